@@ -9,7 +9,7 @@ that is already resident in HBM: the fused launch sfm_loss_fwd_bwd (loss and all
 SFMLearnerLoss.__call__ runs when backprop is enabled).  The path shards over samples with no exchange on the data
 path; under a launcher (any N, N = 1 included) the five REPORTED scalars of EVERY step are summed over the ranks by one
 ncclAllReduce(sum, fp32, count=5) issued straight through librccl on the stream the loss kernels run on (SURVEY.md 8(e);
-sfm-learner-chainer_amd/rccl.py), inside the timed region.  Two other placements are measured in the same N > 1 run and reported
+sfm-learner-chainer_amd/rccl.py), inside the timed region.  Two other placements are measured in the same N > 1 run (--full) and reported
 as secondary keys: `interval_variant` (ONE all-reduce of the K rows per block of K steps) and `per_step_torch_variant` (the
 per-step all-reduce through torch.distributed: 42 us of host time per call).  Workload at any N: BASELINE.json configs[2]/[3] AS WRITTEN -- B = 32 samples PER GPU,
 128x416, 4 scales, 2 sources, L1 + SSIM(0.15, experiments/sfm_learner_v1_ssim.yml) + EDGE-AWARE smoothness(0.1)
@@ -19,11 +19,17 @@ per-step all-reduce through torch.distributed: 42 us of host time per call).  Wo
 `--gpus N` with N > 1 and no torchrun environment: this process starts N ranks itself (as child processes, before
 anything touches a GPU) and returns their exit code.
 
-Timing: W untimed warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both
-sides (max over ranks); blocks are repeated until >= --min-time seconds have been timed, `ms_per_step` is the MEDIAN
-block (p10 / p90 / first block alongside), `value` follows from it.
+Timing: W untimed warm-up steps, one read of the inputs by another kernel, then untimed settling blocks of the same steps
+until >= --min-time seconds have run (the clock ramps up over the first few hundred steps), then ONE block of EXACTLY K
+timed steps, bracketed by barrier + synchronize on both sides (max over ranks): `ms_per_step` = that block / K, `value`
+follows from it.
 Metric: warped output Mpixels/s, pixels := B * n_src * sum_s h_s*w_s per step.
 Prints ONE JSON line on rank 0.
+
+`--dump-outputs DIR`: after the timed block, rank 0 writes what the last timed step computed -- the five scalars and every
+gradient the step returns -- as DIR/<name>.npy (float32); the inputs are seeded, so two builds compare output for output.
+`--full`: everything beyond the headline as well -- the pre-warm level, the secondary workloads and paths, the CPU baseline,
+and at N > 1 the other placements of the collective and the all-reduce probe.  A plain run measures the headline only.
 """
 import argparse
 import ctypes as C
@@ -328,6 +334,30 @@ def warm_inputs(runner):
     return acc
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, torch, np, runner, loss_row):
+    """--dump-outputs: what a caller of the timed step receives from its last launch -- the five scalars (loss5) and the gradients
+    w.r.t. every disparity scale (d_disp_s<s>) and every source pose (d_pose_<i>) -- as float32 DIR/<name>.npy.  Should they exceed
+    DUMP_LIMIT_BYTES in all, every large array is thinned to the same fixed stride of its flattened elements (the same sample on
+    every run)."""
+    torch.cuda.synchronize()
+    fl = runner.fl
+    arrays = {"loss5": loss_row}
+    arrays.update(("d_disp_s%d" % s, t) for s, t in enumerate(fl.d_disps))
+    arrays.update(("d_pose_%d" % i, t) for i, t in enumerate(fl.d_poses))
+    large = lambda t: t.numel() > 1 << 16
+    small_bytes = sum(t.numel() * 4 for t in arrays.values() if not large(t))
+    stride = max(1, -(-sum(t.numel() * 4 for t in arrays.values() if large(t)) // (DUMP_LIMIT_BYTES - small_bytes)))
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        if stride > 1 and large(t):
+            a = np.ascontiguousarray(a.reshape(-1)[::stride])
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def quick(torch, np, ev, runner, min_time=0.12, k=25):
     """Secondary measurement (NOT the headline): blocks of k steps until min_time, median block; kernel times from events."""
     pairs = [[ev.create() for _ in range(4)] for _ in range(k)]
@@ -530,9 +560,15 @@ def main():
                     help="under a launcher: all-reduce the five reported scalars after EVERY step with ncclAllReduce on the compute "
                          "stream (default, SURVEY.md 8(e)); once per block of --steps steps (interval); or after every step through "
                          "torch.distributed.all_reduce (step_torch)")
-    ap.add_argument("--min-time", type=float, default=0.3, help="seconds of timed steps at least (blocks of --steps are repeated)")
-    ap.add_argument("--max-blocks", type=int, default=400)
+    ap.add_argument("--min-time", type=float, default=0.3,
+                    help="seconds of untimed settling steps at least before the timed block (blocks of min(--steps, 1000) are repeated)")
+    ap.add_argument("--max-blocks", type=int, default=400, help="at most this many settling blocks")
     ap.add_argument("--event-every", type=int, default=20, help="attach the kernel-timing events to every n-th timed step (1 = every step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the pre-warm level, the secondary workloads and paths, the CPU "
+                         "baseline; at N > 1 the other placements of the collective and the all-reduce probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (loss scalars, gradients) to DIR/<name>.npy as float32")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -628,21 +664,21 @@ def main():
     # (the sampled steps sit in the MIDDLE of their stretch of ev_every steps: the first step of a block starts on an idle GPU, behind
     #  the barrier + synchronize that opens the block, and is not representative of the steps the block is timed over)
     # Round 5: with the driver's K = 20 one sampled step per block was 0.25 us on every step of the headline.  The stretch between two
-    # sampled steps is now counted ACROSS blocks and, once the number of blocks is known, widened so that the whole timed region carries
-    # about EVENT_SAMPLES of them (never more often than --event-every): the kernel's mean duration rests on as many launches as it
-    # needs, and the steps pay for no more.
+    # sampled steps is now counted ACROSS blocks and, once the number of blocks is known, widened so that the settling blocks and the
+    # timed block together carry about EVENT_SAMPLES of them (never more often than --event-every): the kernel's mean duration rests on
+    # as many launches as it needs, and the steps pay for no more.
     EVENT_SAMPLES = 64
     sample_state = {"stretch": ev_every, "count": 0, "next": min(ev_every, K) // 2}
     max_per_block = K // ev_every + 1
     event_pool = [[ev.create() for _ in range(4)] for _ in range(max_per_block)]
     events = {}          # step index within the CURRENT block -> its four events
 
-    def plan_block_samples():
+    def plan_block_samples(n):
         events.clear()
         st = sample_state
-        for k in range(K):
+        for k in range(n):
             # (never the first or the last step of a block: they border on the block's barrier + synchronize)
-            if st["count"] >= st["next"] and (K <= 2 or 0 < k < K - 1) and len(events) < max_per_block:
+            if st["count"] >= st["next"] and (n <= 2 or 0 < k < n - 1) and len(events) < max_per_block:
                 events[k] = event_pool[len(events)]
                 st["next"] = st["count"] + st["stretch"]
             st["count"] += 1
@@ -657,14 +693,14 @@ def main():
         if collective == "interval":
             reduce_rows(loss_log[:n])
 
-    def timed_block(collective):
-        plan_block_samples()
+    def timed_block(collective, n):
+        plan_block_samples(n)
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_steps(K, collective, True)
+        run_steps(n, collective, True)
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
@@ -687,11 +723,11 @@ def main():
     input_warm = not args.no_input_warm
     global INPUT_WARM
     INPUT_WARM = input_warm
-    # Round 6 (round-5 verdict item 6 / advisor): the level BEFORE that read is measured and put on the line too -- about twenty blocks
-    # of the same K steps in the state the set-up left, `pre_warm_ms_per_step`: the figure that compares with the lines of rounds 1-4,
-    # which had no such read.  (No kernel events on these blocks.)
+    # Round 6 (round-5 verdict item 6 / advisor): the level BEFORE that read is measured and put on the line too (--full) -- about twenty
+    # blocks of the same K steps in the state the set-up left, `pre_warm_ms_per_step`: the figure that compares with the lines of rounds
+    # 1-4, which had no such read.  (No kernel events on these blocks.)
     pre_warm = None
-    if input_warm:
+    if input_warm and args.full:
         events.clear()
         pw = []
         # (the SAME number of blocks on every rank -- they hold collectives -- so it follows from K alone, never from a clock: about
@@ -706,34 +742,43 @@ def main():
             torch.cuda.synchronize()
             pw.append((time.perf_counter() - t0) / K)
         pre_warm = float(np.median(pw)) * 1e3
+    if input_warm:
         warm_inputs(R)
         run_steps(min(args.warmup, 5), coll, False)
-    blocks, k_main, k_second = [], [], []
+    settle, k_main, k_second = [], [], []
 
     def collect_kernel_times():
         k_main.extend(ev.elapsed_ms(e[0], e[1]) for e in events.values())
         if args.mode == "separate":
             k_second.extend(ev.elapsed_ms(e[2], e[3]) for e in events.values())
 
-    blocks.append(timed_block(coll))
+    # Settling blocks before the timed one: after the set-up and the read above the clock ramps up over the first few hundred steps
+    # (the first blocks of a run were up to 12 % slower than its median), so the K timed steps start on a GPU at its steady state.
+    # They carry kernel events like the timed block; their own times are on the line as timing.settle_*.
+    KS = min(K, 1000)
+    settle.append(timed_block(coll, KS))
     collect_kernel_times()
-    n_blocks = int(min(args.max_blocks, max(1, np.ceil(args.min_time / max(blocks[0], 1e-9)))))   # the same on every rank
-    sample_state["stretch"] = max(ev_every, (n_blocks * K) // EVENT_SAMPLES)
-    for _ in range(n_blocks - 1):
-        blocks.append(timed_block(coll))
+    n_settle = int(min(args.max_blocks, max(1, np.ceil(args.min_time / max(settle[0], 1e-9)))))   # the same on every rank
+    sample_state["stretch"] = max(ev_every, (n_settle * KS + K) // EVENT_SAMPLES)
+    for _ in range(n_settle - 1):
+        settle.append(timed_block(coll, KS))
         collect_kernel_times()
+    timed_s = timed_block(coll, K)
+    collect_kernel_times()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, R, loss_log[K - 1])
     loss = loss_log[K - 1].cpu().numpy().tolist()
-    per_step = np.array(blocks) / K
-    ms_step = float(np.median(per_step)) * 1e3
+    ms_step = timed_s / K * 1e3
+    settle_per_step = np.array(settle) / KS
 
     # N > 1: the same with the other placement of the collective, and the all-reduce of a DispNet+PoseNet-sized gradient buffer
     # (characterises xGMI; not part of this path)
     variants_ms, allreduce_probe = {}, None
-    if use_dist:      # (also at N = 1 under the launcher: the same calls on a one-rank communicator)
+    if use_dist and args.full:      # (also at N = 1 under the launcher: the same calls on a one-rank communicator)
         for oc in other_colls:
             run_steps(min(args.warmup, 3), oc, False)
-            variants_ms[oc] = float(np.median([timed_block(oc) for _ in range(min(n_blocks, 5))])) / K * 1e3
-    if world > 1:
+            variants_ms[oc] = float(np.median([timed_block(oc, K) for _ in range(min(n_settle, 5))])) / K * 1e3
+    if world > 1 and args.full:
         buf = torch.zeros((GRAD_BUFFER_FLOATS,), dtype=torch.float32, device=dev)
         # through the direct communicator when there is one: the bus-bandwidth figure is then RCCL's, not that of torch's host path
         big_reduce = (lambda: comm.all_reduce_sum_f32(buf, raw_stream)) if comm is not None else (lambda: dist.all_reduce(buf))
@@ -759,9 +804,9 @@ def main():
                                    "timed only to characterise RCCL over xGMI on this node"}
         del buf
 
-    # secondary measurements (NOT part of the timed blocks above), rank 0 of a single-GPU run only
+    # secondary measurements (--full; NOT part of the timed block above), rank 0 of a single-GPU run only
     secondary = {}
-    if world == 1 and not args.no_secondary:
+    if world == 1 and args.full and not args.no_secondary:
         def guarded(name, fn):
             try:
                 secondary[name] = fn()
@@ -851,17 +896,17 @@ def main():
                        "collective": collective_line(coll, comm is not None, rehearse, comm_note) if use_dist else None,
                        "parallelism": ("batch-sharded x%d, no exchange on the data path; RCCL all-reduce of the 5 reported scalars: %s" % (
                            world, COLLECTIVE_NOTES[coll])) if use_dist else "single GPU, no collective"},
-            "timing": {"blocks": len(blocks), "steps_per_block": K, "timed_s": round(float(np.sum(blocks)), 4),
-                       "ms_per_step_median": round(ms_step, 5), "ms_per_step_p10": round(float(np.percentile(per_step, 10)) * 1e3, 5),
-                       "ms_per_step_p90": round(float(np.percentile(per_step, 90)) * 1e3, 5),
-                       "ms_per_step_first_block": round(float(per_step[0]) * 1e3, 5), "ms_per_step_min": round(float(per_step.min()) * 1e3, 5),
-                       # the blocks in time order, thinned to at most 48 entries: how the box's state moved while it was measured
-                       "ms_per_step_series": [round(float(v) * 1e3, 4) for v in per_step[::max(1, len(per_step) // 48)]]},
+            "timing": {"timed_steps": K, "timed_s": round(timed_s, 6),
+                       "settle_blocks": len(settle), "settle_steps_per_block": KS, "settle_s": round(float(np.sum(settle)), 4),
+                       "settle_ms_per_step_median": round(float(np.median(settle_per_step)) * 1e3, 5),
+                       "settle_ms_per_step_first_block": round(float(settle_per_step[0]) * 1e3, 5),
+                       # the settling blocks in time order, thinned to at most 48 entries: how the box's state moved before the timed block
+                       "settle_ms_per_step_series": [round(float(v) * 1e3, 4) for v in settle_per_step[::max(1, len(settle_per_step) // 48)]]},
             "roofline": roofline,
             "roofline_valu": roofline_valu,
             "roofline_valu_null_because": facts["stale"] if roofline_valu is None else None,
             "step_roofline_frac": round((BYTES_FWD + BYTES_BWD) * R.warped_px / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            # the same blocks BEFORE the one-off read of the inputs (config.input_warm_read): the protocol of rounds 1-4
+            # (--full) the same blocks BEFORE the one-off read of the inputs (config.input_warm_read): the protocol of rounds 1-4
             "pre_warm_ms_per_step": round(pre_warm, 5) if pre_warm else None,
             "pre_warm_step_roofline_frac": round((BYTES_FWD + BYTES_BWD) * R.warped_px / (pre_warm * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if pre_warm else None,
             "csrc_sha16": csrc_sha16(),
@@ -870,14 +915,14 @@ def main():
         for oc, ms in variants_ms.items():
             out[VARIANT_KEYS[oc]] = {"ms_per_step": round(ms, 5), "value": round(R.warped_px * world / (ms * 1e-3) / 1e6, 1),
                                      "note": COLLECTIVE_NOTES[oc]}
-        if world > 1:
+        if world > 1 and args.full:
             out["allreduce_160MB"] = allreduce_probe
         if rehearse:
             out["rehearsal"] = ("SFM_BENCH_REHEARSE_ONE_GPU: all %d ranks ran on ONE GPU and the collectives went through gloo -- this line "
                                 "exercises the N > 1 code path, it is NOT a measurement" % world)
             out["config"]["parallelism"] = "REHEARSAL on one GPU (gloo): " + out["config"]["parallelism"]
         out.update(secondary)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if comm is not None:

@@ -16,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(600)
 def test_two_ranks_on_one_gpu(dev):
     env = dict(os.environ, SFM_BENCH_REHEARSE_ONE_GPU="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-secondary",
-                        "--no-cpu-baseline", "--min-time", "0.01"], env=env, capture_output=True, text=True, timeout=580, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full",
+                        "--no-secondary", "--no-cpu-baseline", "--min-time", "0.01"], env=env, capture_output=True, text=True, timeout=580, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:]                # rank 0 alone prints
@@ -44,7 +44,7 @@ def test_drivers_launcher_form_runs_on_real_rccl_at_one_rank(dev):
     init_process_group("nccl"), the communicator bench.py makes through librccl (rccl.py), the per-step ncclAllReduce on the
     compute stream, the per-interval and the torch.distributed variants and the barrier + MAX timing all execute on RCCL; the
     line must be the plain N = 1 line to within 10 % (a one-rank all-reduce costs a step nothing; see the assertion for the margin)."""
-    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-secondary", "--no-cpu-baseline"]
+    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-secondary", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     bench = os.path.join(ROOT, "bench.py")

@@ -17,6 +17,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHECK = "--check" in sys.argv          # recompute from the sources and compare with the committed JSON instead of writing it
@@ -76,10 +77,11 @@ def main():
     for line in open(os.path.join(CSRC, "Makefile")):
         if line.startswith("CXXFLAGS"):
             flags = line.split("=", 1)[1].replace("$(ARCH)", "gfx950").split()
-    asm = "/tmp/sfm_loss_issue_model.s"
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in flags if f != "-fPIC"] + ["-S", "--cuda-device-only", "sfm_loss.hip", "-o", asm],
-                          cwd=CSRC, stderr=subprocess.DEVNULL)
-    lines = open(asm).read().split("\n")
+    with tempfile.TemporaryDirectory() as tmp:       # (a private directory: a fixed file name may belong to another user)
+        asm = os.path.join(tmp, "sfm_loss_issue_model.s")
+        subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in flags if f != "-fPIC"] + ["-S", "--cuda-device-only", "sfm_loss.hip", "-o", asm],
+                              cwd=CSRC, stderr=subprocess.DEVNULL)
+        lines = open(asm).read().split("\n")
     starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN3sfm(11loss_kernel|16loss_kernel_wide)I.*:", l)]
     out = {"tag": tag, "kernels": {}}
     for n, st in enumerate(starts):
