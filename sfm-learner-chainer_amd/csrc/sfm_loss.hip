@@ -529,12 +529,15 @@ static int make_plan(const SfmLossDesc* d, bool grad, bool need_loss, bool need_
       A.d_pose[i] = d->d_pose[i];
     }
   }
-  // the optional warped-image output: an array for every scale or for none
+  // the optional warped-image output: an array for every scale or for none.  Which kernel runs follows from the descriptor's
+  // pointers whatever need_outputs says, so that sfm_loss_plan_info reports the launch the call will make; only the
+  // validation of the output arrays is left to the calls that write them.
   p.warped = false;
-  if (need_loss && need_outputs) {
+  if (need_loss) {
     int n_w = 0;
     for (int s = 0; s < d->n_scales; ++s) n_w += d->warped[s] != nullptr;
-    if (n_w != 0 && n_w != d->n_scales) return fail(SFM_ERR_NULL, "sfm_loss: warped[] is set for %d of %d scales (all or none)", n_w, d->n_scales);
+    if (need_outputs && n_w != 0 && n_w != d->n_scales)
+      return fail(SFM_ERR_NULL, "sfm_loss: warped[] is set for %d of %d scales (all or none)", n_w, d->n_scales);
     p.warped = n_w != 0;
   }
   const int sw = strip_width(p.ssim, grad, p.smode);
@@ -546,7 +549,7 @@ static int make_plan(const SfmLossDesc* d, bool grad, bool need_loss, bool need_
   const int cus = device_cus();
   // (a launch is "small" when even at the smallest chunk height its waves fit the SIMDs three deep)
   p.dsrc = false;
-  if (grad && need_outputs)
+  if (grad)
     for (int s = 0; s < d->n_scales; ++s) p.dsrc = p.dsrc || d->d_src[s] != nullptr;
   p.wide = grad && !p.dsrc && !p.ref && !p.ssim && !p.expl && !tuning().no_wide && max_items(d, sw) <= (long long)cus * 4 * 3;
   // Two sources per pass (loss_kernel_pair): the SSIM gradient launches of the pixel-interleaved layout with an even number of

@@ -838,8 +838,36 @@ def test_reference_order_projection_every_mode_entry_point_and_layout(ops, synth
         np.testing.assert_allclose(b, a, rtol=0, atol=2e-5 * max(np.abs(a).max(), 1e-30))
 
 
+def traced_items(ops, fl, launch):
+    """Work items the main kernel of ONE launch really ran: sfm_loss_debug_trace makes every wavefront of the next sfm_loss_* call
+    write a 32-byte record {start, end, HW_ID, XCC_ID} (start > 0) at its item's index.  The buffer is sized by the header's own
+    bound (items <= sfm_loss_workspace_bytes / 64), never by sfm_loss_plan_info -- that is the number under test."""
+    import ctypes as C
+    import torch
+    n_rec = ops.lib.sfm_loss_workspace_bytes(C.byref(fl.desc)) // 64
+    assert n_rec > 0
+    buf = torch.zeros((n_rec, 4), dtype=torch.int64, device=fl.device)
+    torch.cuda.synchronize()
+    ops.check(ops.lib.sfm_loss_debug_trace(C.c_void_p(buf.data_ptr())))
+    launch()
+    torch.cuda.synchronize()
+    return int((buf != 0).any(dim=1).sum().item())
+
+
+def planned_items(ops, fl, grad, loss):
+    import ctypes as C
+    out = (C.c_int * (1 + 4 * fl.desc.n_scales))()
+    ops.check(ops.lib.sfm_loss_plan_info(C.byref(fl.desc), grad, loss, out, len(out)))
+    return out[0]
+
+
+# (B = 8 at 128x416: the smallest reference-sized batch whose one-source chunks are taller than the 4-row minimum, so that the two
+#  forms plan different item counts -- below it both cut every scale into 4-row chunks and run as many items)
+PAIR_SHAPES = [(2, 32, 48, 2, 3), (3, 20, 130, 4, 2), (4, 128, 416, 2, 4), (1, 37, 70, 6, 1), (8, 128, 416, 2, 4)]
+
+
 @pytest.mark.parametrize("cfg_name", ["ssim_smooth", "ssim_only", "edge_aware"])
-@pytest.mark.parametrize("shape", [(2, 32, 48, 2, 3), (3, 20, 130, 4, 2), (4, 128, 416, 2, 4), (1, 37, 70, 6, 1)])
+@pytest.mark.parametrize("shape", PAIR_SHAPES)
 def test_two_sources_per_pass_gives_the_one_source_results(ops, synth, dev, cfg_name, shape):
     """loss_kernel_pair (sfm_ssim_pair.h, round 6): SSIM gradient launches of an even number of sources can walk TWO sources per pass
     at two waves per SIMD (the library picks that form where it is faster: small batches; profiles/r06_pair_kernel.txt).  Per pixel
@@ -866,12 +894,59 @@ def test_two_sources_per_pass_gives_the_one_source_results(ops, synth, dev, cfg_
     what = "TWO SOURCES PER PASS %s B=%d %dx%d %d src" % (cfg_name, B, H, W, n_src)
     _check_losses(fl.forward_backward(variant=5), ref)
     _check_grads(fl, ref, n_src, what=what, **knife_widths(d, ref))
-    # the form is really another kernel with another plan: fewer work items (host-side query; variant hooks do not reach it, the
-    # environment does -- so only the default is asserted: small launches take the pair form)
-    import ctypes as C
-    out = (C.c_int * (1 + 4 * n_scales))()
-    ops.check(ops.lib.sfm_loss_plan_info(C.byref(fl.desc), 1, 1, out, len(out)))
-    assert out[0] > 0
+    # the variants are two kernels with two plans: the pair form's chunks are taller, so it runs no more work items than the
+    # one-source form (counted on the device) -- strictly fewer unless both are at the 4-row minimum chunk, which is where the count
+    # cannot tell them apart (test_two_sources_per_pass_is_the_default_of_some_small_launch needs a shape where it can).  The
+    # default launch runs exactly what sfm_loss_plan_info reports, and that is one of the two (which one is make_plan's choice).
+    items = {v: traced_items(ops, fl, lambda: fl.forward_backward(variant=v)) for v in (4, 5)}
+    default = traced_items(ops, fl, fl.forward_backward)
+    planned = planned_items(ops, fl, 1, 1)
+    parity_note("two sources per pass %s B=%d %dx%d %d src: items one-source %d, pair %d, default %d (planned %d)" % (
+        cfg_name, B, H, W, n_src, items[4], items[5], default, planned))
+    assert 0 < items[5] <= items[4], items
+    assert default == planned and default in (items[4], items[5]), (default, planned, items)
+
+
+@pytest.mark.parametrize("cfg_name", ["ssim_smooth", "ssim_only", "edge_aware"])
+def test_two_sources_per_pass_is_the_default_of_some_small_launch(ops, synth, dev, cfg_name):
+    """What the pair-form test above cannot see from one shape: over its shapes, at least one default launch (a small batch) IS the
+    two-sources-per-pass launch -- the traced item count of the default equals that of sfm_loss_variant(5) and is below that of
+    (4), so the hook really switched the kernel.  Which shapes do is left to make_plan."""
+    taken = []
+    for shape in PAIR_SHAPES:
+        B, H, W, n_src, n_scales = shape
+        d = synth.make_inputs(B=B, H=H, W=W, n_src=n_src, n_scales=n_scales, seed=23)
+        fl = _bind(ops, dev, d, CONFIGS[cfg_name], layout="hwc")
+        items = {v: traced_items(ops, fl, lambda: fl.forward_backward(variant=v)) for v in (4, 5)}
+        default = traced_items(ops, fl, fl.forward_backward)
+        assert default in (items[4], items[5]), (shape, default, items)
+        if default == items[5] < items[4]:
+            taken.append(shape)
+    parity_note("pair form by default (%s): %s" % (cfg_name, taken))
+    assert taken, "no shape of %s takes the two-sources-per-pass form by default" % PAIR_SHAPES
+
+
+@pytest.mark.parametrize("case", [
+    # (config, B, H, W, n_src, n_scales, layout): SSIM + HWC + even sources (two sources per pass without the outputs) at a small
+    # and at the reference's batch, and an L1-only small launch (the wide form without the outputs)
+    ("ssim_smooth", 2, 32, 48, 2, 3, "hwc"), ("ssim_smooth", 8, 128, 416, 2, 4, "hwc"), ("l1", 2, 32, 48, 2, 3, "planar"),
+    ("l1_smooth", 1, 37, 70, 4, 2, "hwc"),
+])
+@pytest.mark.parametrize("output", ["d_src", "warped"])
+def test_plan_info_counts_the_items_of_launches_with_outputs(ops, synth, dev, case, output):
+    """sfm_loss_plan_info(desc, grad, loss)[0] is the number of work items the main kernel of that entry point runs for `desc`
+    -- also for a descriptor that binds d_src (no pair or wide form: the d_src kernels) or warped (no pair form), which decide
+    the kernel as much as the loss configuration does.  Each entry point that uses the output: its traced item count."""
+    cfg_name, B, H, W, n_src, n_scales, layout = case
+    d = synth.make_inputs(B=B, H=H, W=W, n_src=n_src, n_scales=n_scales, seed=29)
+    fl = _bind(ops, dev, d, CONFIGS[cfg_name], layout=layout, want_d_src=output == "d_src", want_warped=output == "warped")
+    entries = {(1, 1): fl.forward_backward, (1, 0): lambda: fl.backward(1.0)} if output == "d_src" else \
+        {(1, 1): fl.forward_backward, (0, 1): fl.forward}
+    for (grad, loss), launch in entries.items():
+        traced, planned = traced_items(ops, fl, launch), planned_items(ops, fl, grad, loss)
+        parity_note("plan_info %s B=%d %dx%d %d src %s with %s, entry (%d,%d): planned %d, traced %d" % (
+            cfg_name, B, H, W, n_src, layout, output, grad, loss, planned, traced))
+        assert traced > 0 and planned == traced, (grad, loss, planned, traced)
 
 
 @pytest.mark.parametrize("layout", ["planar", "hwc"])
