@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 5
+#define SFM_ABI_VERSION 6
 
 #define SFM_OK 0
 #define SFM_ERR_NULL (-1)      /* a required pointer is NULL                       */
@@ -258,6 +258,17 @@ int sfm_step_fwd_bwd(const float *tgt_full, const float *src_full, const SfmLoss
 int sfm_disp_act_fwd(const float *const *x, float *const *disp, const long long *numel, int n_scales, void *stream);
 int sfm_disp_act_bwd(const float *const *disp, const float *const *g_disp, float *const *g_x, const long long *numel,
                      int n_scales, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The gradients of a gy = 1 backward (sfm_loss_fwd_bwd, sfm_step_fwd_bwd) scaled by an upstream gradient that lives on the
+ * DEVICE (ABI v6): the 0-d grad_output an autograd engine hands over, read by the kernel, never by the host -- so the scaling
+ * needs no device sync and can be captured in a graph.
+ *   y[k][j] = x[k][j] * gy[0] for k < n, j < numel[k]: ONE IEEE fp32 multiply per element (bitwise x * gy, for gy = +-0, inf and
+ *   NaN too).  One launch for all n <= 32 arrays (d_disp x8, d_pose x8, d_mask x8, d_src x8).  y[k] == x[k] (in place) is
+ *   allowed, partial overlap is not.  numel[k] == 0 skips array k (its pointers may be NULL); a total of 0 launches nothing.
+ * Errors: x, y, numel or gy NULL -> SFM_ERR_NULL; n outside 1..32 or numel[k] < 0 -> SFM_ERR_SHAPE (checked before any HIP call).
+ * ---------------------------------------------------------------------------------------- */
+int sfm_scale_arrays(const float *const *x, float *const *y, const long long *numel, int n, const float *gy, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * data_augmentation(), datasets/kitti/kitti_raw_transformed.py:23-74, image side: random scaling

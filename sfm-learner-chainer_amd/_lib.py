@@ -16,7 +16,7 @@ import torch  # noqa: F401
 
 SFM_MAX_SCALES = 8
 SFM_MAX_SRC = 8
-SFM_ABI_VERSION = 5
+SFM_ABI_VERSION = 6
 SFM_LAYOUT_PLANAR, SFM_LAYOUT_HWC = 0, 1
 SFM_PROJECTION_FAST, SFM_PROJECTION_REFERENCE_ORDER = 0, 1
 PROJECTIONS = {None: SFM_PROJECTION_FAST, "fast": SFM_PROJECTION_FAST, "reference_order": SFM_PROJECTION_REFERENCE_ORDER}
@@ -76,6 +76,7 @@ SYMBOLS = {
     "sfm_resize_fwd": (_I, [_FP, _FP, _I, _I, _I, _I, _I, _I, _V]),
     "sfm_disp_act_fwd": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), _I, _V]),
     "sfm_disp_act_bwd": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), _I, _V]),
+    "sfm_scale_arrays": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), _I, _FP, _V]),
     "sfm_augment_fwd": (_I, [_FP, _FP, _FP, _I, _I, _I, _I, _I, _V]),
     "sfm_pyramid_fwd": (_I, [_FP, C.POINTER(C.c_void_p), _I, _I, _I, _I, _I, _V]),
     "sfm_pyramid_variant": (_I, [_I]),

@@ -925,6 +925,85 @@ static int disp_act_launch(bool bwd, const float* const* a, const float* const* 
   return check_launch(who);
 }
 
+// ------------------------------------------------------------------------------------------
+// The gradients of a gy = 1 backward scaled by the upstream gradient the autograd engine hands over (torch_api.py):
+//   y[k][j] = x[k][j] * gy[0], gy read from DEVICE memory, for up to 32 arrays in one launch.
+// Blocks are dealt to the arrays in proportion to their length (block_begin: prefix offsets), so a block works on ONE array and
+// every pointer it needs is a uniform load; inside its array a block grid-strides over 16-byte vectors, with a scalar head up to the
+// first 16-byte boundary (when x and y share one) and a scalar tail.
+// ------------------------------------------------------------------------------------------
+constexpr int SCALE_MAX_ARRAYS = 32;
+constexpr int SCALE_THREADS = 256;
+constexpr long long SCALE_MAX_BLOCKS = 2048;      // ~256 CUs x 8: grid-stride beyond (memory-bound)
+
+struct ScaleArgs {
+  const float* x[SCALE_MAX_ARRAYS];
+  float* y[SCALE_MAX_ARRAYS];
+  long long numel[SCALE_MAX_ARRAYS];
+  long long head[SCALE_MAX_ARRAYS];          // scalar elements before the vector body (numel: x, y not co-aligned)
+  int block_begin[SCALE_MAX_ARRAYS + 1];     // blocks [block_begin[k], block_begin[k+1]) work on array k
+  int n;
+};
+
+__global__ __launch_bounds__(SCALE_THREADS) void scale_arrays_kernel(const ScaleArgs A, const float* gy) {
+  const int b = blockIdx.x;
+  int k = 0;
+  for (int i = 1; i < A.n; ++i)
+    if (b >= A.block_begin[i]) k = i;
+  const float g = *gy;
+  const float* x = A.x[k];
+  float* y = A.y[k];                                 // may equal x (in place): no __restrict__
+  const long long n = A.numel[k], h = A.head[k];
+  const long long stride = (long long)(A.block_begin[k + 1] - A.block_begin[k]) * SCALE_THREADS;
+  const long long t = (long long)(b - A.block_begin[k]) * SCALE_THREADS + threadIdx.x;
+  for (long long j = t; j < h; j += stride) y[j] = x[j] * g;
+  const long long nv = (n - h) >> 2;
+  const float4* xv = reinterpret_cast<const float4*>(x + h);
+  float4* yv = reinterpret_cast<float4*>(y + h);
+  for (long long j = t; j < nv; j += stride) {
+    float4 v = xv[j];
+    v.x = v.x * g; v.y = v.y * g; v.z = v.z * g; v.w = v.w * g;
+    yv[j] = v;
+  }
+  const long long tail = h + (nv << 2);
+  if (t < n - tail) y[tail + t] = x[tail + t] * g;
+}
+
+static int scale_arrays_launch(const float* const* x, float* const* y, const long long* numel, int n, const float* gy,
+                               void* stream) {
+  const char* who = "sfm_scale_arrays";
+  SFM_REQUIRE(x && y && numel, SFM_ERR_NULL, "%s: NULL pointer", who);
+  SFM_REQUIRE(n >= 1 && n <= SCALE_MAX_ARRAYS, SFM_ERR_SHAPE, "%s: n=%d, need 1..%d", who, n, SCALE_MAX_ARRAYS);
+  SFM_REQUIRE(gy, SFM_ERR_NULL, "%s: NULL gy", who);
+  ScaleArgs A;
+  A.n = n;
+  long long want[SCALE_MAX_ARRAYS], total = 0;
+  for (int k = 0; k < n; ++k) {
+    SFM_REQUIRE(numel[k] >= 0, SFM_ERR_SHAPE, "%s: numel[%d] < 0", who, k);
+    SFM_REQUIRE(numel[k] == 0 || (x[k] && y[k]), SFM_ERR_NULL, "%s: NULL array %d", who, k);
+    A.x[k] = x[k]; A.y[k] = y[k]; A.numel[k] = numel[k];
+    const uintptr_t ax = (uintptr_t)x[k], ay = (uintptr_t)y[k];
+    const long long head = ((ax & 15) == (ay & 15) && (ax & 3) == 0) ? (long long)((16 - (ax & 15)) & 15) / 4 : numel[k];
+    A.head[k] = head < numel[k] ? head : numel[k];
+    const long long units = A.head[k] + ((numel[k] - A.head[k] + 3) >> 2);    // threads' worth of work
+    want[k] = (units + SCALE_THREADS - 1) / SCALE_THREADS;
+    total += want[k];
+  }
+  if (total == 0) return SFM_OK;
+  // each non-empty array gets its share of at most SCALE_MAX_BLOCKS blocks, and at least one
+  A.block_begin[0] = 0;
+  for (int k = 0; k < n; ++k) {
+    long long nb = want[k];
+    if (total > SCALE_MAX_BLOCKS && nb > 0) {
+      nb = (long long)((double)nb * (double)SCALE_MAX_BLOCKS / (double)total);
+      if (nb < 1) nb = 1;
+    }
+    A.block_begin[k + 1] = A.block_begin[k] + (int)nb;
+  }
+  hipLaunchKernelGGL(scale_arrays_kernel, dim3(A.block_begin[n]), dim3(SCALE_THREADS), 0, (hipStream_t)stream, A, gy);
+  return check_launch(who);
+}
+
 }  // namespace sfm
 
 using namespace sfm;
@@ -933,6 +1012,10 @@ extern "C" {
 
 int sfm_abi_version(void) { return SFM_ABI_VERSION; }
 const char* sfm_last_error(void) { return sfm::g_err; }
+
+int sfm_scale_arrays(const float* const* x, float* const* y, const long long* numel, int n, const float* gy, void* stream) {
+  return scale_arrays_launch(x, y, numel, n, gy, stream);
+}
 
 
 int sfm_pose_proj_fwd(const float* pose6, const float* K, float* proj, int N, void* stream) {

@@ -1,0 +1,515 @@
+"""PyTorch autograd route to the fused loss and to the operators.
+
+The reference's networks (DispNet, PoseNet) are Chainer links; on this stack they are `torch.nn` modules whose outputs carry a
+grad_fn.  This module hands those outputs to libsfmwarp and the gradients it computes back to torch.autograd:
+
+  sfm_learner_loss / SFMLearnerLoss   the loss of models/base_model.py:48-124 as a function and as a torch.nn.Module
+  projective_inverse_warp             models/transform.py:156-193 (ops.warp_fwd / ops.warp_bwd)
+  disp_activation                     models/disp_net.py:104-122 (ops.disp_act_fwd / ops.disp_act_bwd)
+
+The loss is two custom operators (torch.library), so that FakeTensor and torch.compile can trace it:
+
+  sfmwarp::sfm_learner_loss   ONE fused call computes the five scalars and, when a gradient is wanted, every gradient for gy = 1
+                              (sfm_step_fwd_bwd; the planar pyramid + sfm_loss_fwd_bwd for frames of HWC_MAX_PIXELS or more)
+  sfmwarp::scale_arrays       its backward: those gradients times the upstream gradient, which the kernel reads on the device
+                              (sfm_scale_arrays), written out of place
+
+Eagerly the same launches run through a torch.autograd.Function (_LossFunction): the generic argument handling of a Python custom
+operator costs more host time per call than a whole step at the reference's batch.  torch.compile traces the operators.
+
+Nothing here reads a device value on the host: a step runs under torch.cuda.graph capture, GradScaler, autocast and
+torch.compile (backend="aot_eager" keeps the hot path in libsfmwarp: no generated kernels).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+from torch import Tensor
+
+from . import _lib, ops
+from ._lib import SfmLossDesc, check, lib
+from .links import HWC_MAX_PIXELS, parse_dict
+
+__all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "scale_arrays_into"]
+
+_ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
+_MAX_ARRAYS = 32             # sfm_scale_arrays
+_FLOATS = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _round(n):
+    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def _grad_spans(disps, poses, masks):
+    """[offset0, numel0, offset1, numel1, ...] of the unit-gradient arrays d_disp[s], d_pose[i], d_mask[s] (in that order) inside
+    the one buffer the loss op returns, and that buffer's length in floats."""
+    spans, off = [], 0
+    for t in list(disps) + list(poses) + list(masks):
+        n = t.numel()
+        spans += [off, n]
+        off += _round(n)
+    return spans, off
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# sfm_scale_arrays
+# ---------------------------------------------------------------------------------------------------------------------------
+def _launch_scale(xp, yp, numel, gy, device):
+    n = len(numel)
+    ptr = C.c_void_p * n
+    args = (ptr(*xp), ptr(*yp), (C.c_longlong * n)(*numel), n, C.c_void_p(gy.data_ptr()))
+    idx = device.index
+    if torch.cuda.current_device() == idx:
+        check(lib.sfm_scale_arrays(*args, ops._stream(idx)))
+    else:
+        with torch.cuda.device(device):
+            check(lib.sfm_scale_arrays(*args, ops._stream(idx)))
+
+
+def _gy(gy):
+    gy = ops._dev(gy, "gy")
+    if gy.numel() != 1:
+        raise TypeError("gy must hold one element, got shape %s" % (tuple(gy.shape),))
+    return gy
+
+
+def scale_arrays_into(xs, ys, gy):
+    """ys[k][...] = xs[k] * gy for up to 32 float32 device arrays in ONE launch (sfm_scale_arrays).  gy: a float32 device tensor of
+    one element, read by the kernel (no host sync).  ys[k] may be xs[k] (in place); contiguous arrays of equal sizes only."""
+    if len(xs) != len(ys) or not 1 <= len(xs) <= _MAX_ARRAYS:
+        raise TypeError("scale_arrays_into: 1..%d arrays and as many outputs, got %d and %d" % (_MAX_ARRAYS, len(xs), len(ys)))
+    gy = _gy(gy)
+    for k, (x, y) in enumerate(zip(xs, ys)):
+        for t, name in ((x, "xs[%d]" % k), (y, "ys[%d]" % k)):
+            ops._dev(t, name)
+            if not t.is_contiguous():
+                raise TypeError("%s: expected a contiguous array" % name)
+            if t.device != gy.device:
+                raise TypeError("%s lives on %s, gy on %s" % (name, t.device, gy.device))
+        if x.numel() != y.numel():
+            raise TypeError("xs[%d] has %d elements, ys[%d] %d" % (k, x.numel(), k, y.numel()))
+    _launch_scale([x.data_ptr() for x in xs], [y.data_ptr() for y in ys], [x.numel() for x in xs], gy, gy.device)
+    return ys
+
+
+def _check_spans(spans, n):
+    """spans = [offset0, numel0, ...]: at most 32 pairs, every span inside a buffer of n elements (before any launch)."""
+    if len(spans) % 2 or len(spans) > 2 * _MAX_ARRAYS:
+        raise TypeError("scale_arrays: spans must hold at most %d (offset, numel) pairs, got %d values" % (_MAX_ARRAYS, len(spans)))
+    for k in range(0, len(spans), 2):
+        o, m = spans[k], spans[k + 1]
+        if o < 0 or m < 0 or o + m > n:
+            raise TypeError("scale_arrays: span %d = (offset %d, numel %d) lies outside x's %d elements" % (k // 2, o, m, n))
+
+
+@torch.library.custom_op("sfmwarp::scale_arrays", mutates_args=())
+def _scale_arrays_op(x: Tensor, spans: list[int], gy: Tensor) -> Tensor:
+    """x: a flat float32 device buffer that holds up to 32 arrays at spans = [offset0, numel0, offset1, numel1, ...] (floats) ->
+    a NEW buffer of x's size whose spans hold x * gy[0], one launch.  Elements outside the spans are not written."""
+    _check_spans(spans, x.numel())
+    x, gy = ops._dev(x, "x", 1), _gy(gy)
+    if gy.device != x.device:
+        raise TypeError("scale_arrays: gy lives on %s, x on %s" % (gy.device, x.device))
+    out = torch.empty_like(x)
+    if spans:
+        xb, yb = x.data_ptr(), out.data_ptr()
+        offs, numel = spans[0::2], spans[1::2]
+        _launch_scale([xb + 4 * o for o in offs], [yb + 4 * o for o in offs], numel, gy, x.device)
+    return out
+
+
+@_scale_arrays_op.register_fake
+def _(x, spans, gy):
+    _check_spans(spans, x.numel())
+    return torch.empty_like(x)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the fused loss
+# ---------------------------------------------------------------------------------------------------------------------------
+class _Plan:
+    """Host-side constants of one configuration (shapes, settings, entry point): the descriptor with everything but the pointers,
+    the workspace size and where each array lies in the per-call scratch buffer.  No device memory."""
+    __slots__ = ("desc", "hwc", "ws_bytes", "tgt_off", "src_off", "ws_off", "scratch", "spans", "grad_floats")
+
+
+_PLANS = {}                 # at most _MAX_PLANS configurations, oldest dropped first
+_MAX_PLANS = 16
+_FAKE = 0x1000             # placeholder pointer for sizing the workspace: never dereferenced
+_desc_hook = None           # measurement hook (tools/torch_step_time.py): called with the descriptor bytes of every launch
+
+
+def _plan(B, H, W, n_src, disps, masks, poses, cfg):
+    S = len(disps)
+    shapes = tuple(tuple(t.shape) for t in disps)
+    key = (B, H, W, n_src, shapes, len(masks), cfg)
+    p = _PLANS.get(key)
+    if p is not None:
+        return p
+    smooth_reg, exp_reg, ssim_rate, smooth_mode, projection, norm_batch = cfg
+    p = _Plan()
+    p.hwc = H * W < HWC_MAX_PIXELS
+    d = SfmLossDesc()
+    d.B, d.norm_B, d.n_src, d.n_scales = B, norm_batch, n_src, S
+    d.smooth_reg, d.exp_reg, d.ssim_rate, d.smooth_mode = smooth_reg, exp_reg, ssim_rate, smooth_mode
+    d.image_layout = _lib.SFM_LAYOUT_HWC if p.hwc else _lib.SFM_LAYOUT_PLANAR
+    d.projection = projection
+    for s in range(S):
+        d.H[s], d.W[s] = shapes[s][2], shapes[s][3]
+        d.tgt[s] = d.src[s] = d.disp[s] = d.d_disp[s] = _FAKE
+        if masks:
+            d.mask_logits[s] = d.d_mask[s] = _FAKE
+    for i in range(n_src):
+        d.pose[i] = d.d_pose[i] = _FAKE
+    d.intrinsics = _FAKE
+    nbytes = lib.sfm_loss_workspace_bytes(C.byref(d)) if B > 0 else 256
+    if nbytes == 0:
+        check(lib.sfm_loss_fwd(C.byref(d), None, None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid loss descriptor")
+    p.desc, p.ws_bytes = bytes(d), nbytes
+    # scratch: the pyramids (hwc: every scale of both; planar: scales 1.. -- scale 0 is the frame itself), then the workspace
+    off, p.tgt_off, p.src_off = 0, [], []
+    for s in range(S):
+        h, w = shapes[s][2], shapes[s][3]
+        if p.hwc or s > 0:
+            p.tgt_off.append(off)
+            off += _round(B * 3 * h * w)
+            p.src_off.append(off)
+            off += _round(B * 3 * n_src * h * w)
+        else:
+            p.tgt_off.append(None)
+            p.src_off.append(None)
+    p.ws_off = off
+    p.scratch = off + _round(nbytes // 4) + _ALIGN    # + the slack to put the workspace on a 256-byte boundary
+    p.spans, p.grad_floats = _grad_spans(disps, poses, masks)
+    if len(_PLANS) >= _MAX_PLANS:
+        _PLANS.pop(next(iter(_PLANS)))            # the oldest configuration (e.g. an epoch's last, smaller batch)
+    _PLANS[key] = p
+    return p
+
+
+def _run_loss(tgt, src, K, disps, poses, masks, cfg, grad):
+    dev = tgt.device
+    B, _, H, W = tgt.shape
+    n_src = len(poses)
+    p = _plan(B, H, W, n_src, disps, masks, poses, cfg)
+    d = SfmLossDesc.from_buffer_copy(p.desc)
+    scratch = torch.empty((p.scratch,), dtype=torch.float32, device=dev)
+    base = scratch.data_ptr()
+    base += (-base) % 256
+    loss5 = torch.empty((5,), dtype=torch.float32, device=dev)
+    g = torch.empty((p.grad_floats if grad else 0,), dtype=torch.float32, device=dev)
+    gb = g.data_ptr()
+    S = len(disps)
+    for s in range(S):
+        d.disp[s] = disps[s].data_ptr()
+        if masks:
+            d.mask_logits[s] = masks[s].data_ptr()
+        if p.tgt_off[s] is None:
+            d.tgt[s], d.src[s] = tgt.data_ptr(), src.data_ptr()
+        else:
+            d.tgt[s], d.src[s] = base + 4 * p.tgt_off[s], base + 4 * p.src_off[s]
+    for i in range(n_src):
+        d.pose[i] = poses[i].data_ptr()
+    d.intrinsics = K.data_ptr()
+    if grad:
+        sp = p.spans
+        for s in range(S):
+            d.d_disp[s] = gb + 4 * sp[2 * s]
+            if masks:
+                d.d_mask[s] = gb + 4 * sp[2 * (S + n_src + s)]
+        for i in range(n_src):
+            d.d_pose[i] = gb + 4 * sp[2 * (S + i)]
+    else:
+        for s in range(S):
+            d.d_disp[s] = d.d_mask[s] = None
+        for i in range(n_src):
+            d.d_pose[i] = None
+    if _desc_hook is not None:
+        _desc_hook(bytes(d))
+    ws = C.c_void_p(base + 4 * p.ws_off)
+    l5 = C.c_void_p(loss5.data_ptr())
+    idx = dev.index
+    guard = torch.cuda.device(dev) if torch.cuda.current_device() != idx else None
+    if guard is not None:
+        guard.__enter__()
+    try:
+        st = ops._stream(idx)
+        if p.hwc:
+            fn = lib.sfm_step_fwd_bwd if grad else lib.sfm_step_fwd
+            check(fn(tgt.data_ptr(), src.data_ptr(), C.byref(d), l5, ws, p.ws_bytes, st))
+        else:
+            for x, pyr, G in ((tgt, d.tgt, 3), (src, d.src, 3 * n_src)):
+                if S > 1:
+                    ptrs = (C.c_void_p * S)(*[pyr[s] for s in range(S)])
+                    check(lib.sfm_pyramid_fwd(x.data_ptr(), ptrs, B, G, H, W, S, st))
+            fn = lib.sfm_loss_fwd_bwd if grad else lib.sfm_loss_fwd
+            check(fn(C.byref(d), l5, ws, p.ws_bytes, st))
+    finally:
+        if guard is not None:
+            guard.__exit__(None, None, None)
+    return loss5, g
+
+
+@torch.library.custom_op("sfmwarp::sfm_learner_loss", mutates_args=())
+def _loss_op(tgt_img: Tensor, src_imgs: Tensor, intrinsics: Tensor, disps: list[Tensor], poses: list[Tensor],
+             masks: list[Tensor], smooth_reg: float, exp_reg: float, ssim_rate: float, smooth_mode: int, projection: int,
+             norm_batch: int, grad: bool) -> list[Tensor]:
+    """The fused loss on validated arrays: tgt_img (B,3,H,W), src_imgs (B,3*n_src,H,W), intrinsics (B,S,3,3), disps[s] (B,1,h,w),
+    poses[i] (B,6), masks[s] (B,n_src,h,w) or no masks (an empty list: no explainability term) -- float32, contiguous, one device.
+    smooth_mode / projection: _lib.SMOOTH_* / _lib.SFM_PROJECTION_*.
+
+    Returns [total (), terms (4,) = (pixel, smooth, exp, ssim), unit_grads]: unit_grads is ONE flat float32 buffer that holds
+    d_disp[s], d_pose[i], d_mask[s] -- the gradients of total for gy = 1, in that order, each at an offset rounded up to 64
+    floats (_grad_spans) -- when `grad`, else empty."""
+    cfg = (float(smooth_reg), float(exp_reg), float(ssim_rate), int(smooth_mode), int(projection), int(norm_batch))
+    loss5, unit = _run_loss(tgt_img, src_imgs, intrinsics, disps, poses, masks, cfg, grad)
+    return [loss5[0], loss5[1:].clone(), unit]          # (an operator's outputs may not share storage)
+
+
+@_loss_op.register_fake
+def _(tgt_img, src_imgs, intrinsics, disps, poses, masks, smooth_reg, exp_reg, ssim_rate, smooth_mode, projection, norm_batch,
+      grad):
+    _, n = _grad_spans(disps, poses, masks)
+    f = dict(dtype=torch.float32, device=tgt_img.device)
+    return [torch.empty((), **f), torch.empty((4,), **f), torch.empty((n if grad else 0,), **f)]
+
+
+def _setup_context(ctx, inputs, output):
+    disps, poses, masks = inputs[3], inputs[4], inputs[5]
+    ctx.spans, _ = _grad_spans(disps, poses, masks)
+    ctx.shapes = [tuple(t.shape) for t in list(disps) + list(poses) + list(masks)]
+    ctx.counts = (len(disps), len(poses), len(masks))
+    ctx.grad = inputs[12]
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.save_for_backward(output[2])
+
+
+def _backward(ctx, grads):
+    S, n, m = ctx.counts
+    (unit,) = ctx.saved_tensors
+    if not ctx.grad:        # no prediction required a gradient (only an image or the intrinsics did): none flows anywhere
+        return (None, None, None, [None] * S, [None] * n, [None] * m, None, None, None, None, None, None, None)
+    gy = grads[0].to(torch.float32)
+    out = torch.ops.sfmwarp.scale_arrays(unit, ctx.spans, gy)
+    sp = ctx.spans
+    views = [out[sp[2 * k]:sp[2 * k] + sp[2 * k + 1]].view(shape) for k, shape in enumerate(ctx.shapes)]
+    return (None, None, None, views[:S], views[S:S + n], views[S + n:], None, None, None, None, None, None, None)
+
+
+_loss_op.register_autograd(_backward, setup_context=_setup_context)
+
+
+def _scaled(unit, spans, shapes, gy):
+    """Eager backward: `unit` times the device scalar gy into a fresh buffer (one sfm_scale_arrays launch), as views of the arrays."""
+    out = torch.empty_like(unit)
+    xb, yb = unit.data_ptr(), out.data_ptr()
+    offs = spans[0::2]
+    _launch_scale([xb + 4 * o for o in offs], [yb + 4 * o for o in offs], spans[1::2], _gy(gy), unit.device)
+    return [out[o:o + n].view(shape) for o, n, shape in zip(offs, spans[1::2], shapes)]
+
+
+class _LossFunction(torch.autograd.Function):
+    """The eager form of sfmwarp::sfm_learner_loss + its autograd: the same launches (_run_loss, sfm_scale_arrays), without the
+    generic argument handling of a Python custom operator (its per-call host cost exceeds a whole step at the reference's batch).
+    torch.compile traces the custom operator instead (sfm_learner_loss)."""
+
+    @staticmethod
+    def forward(ctx, tgt, src, K, cfg, grad, S, n, *arrays):
+        disps, poses, masks = list(arrays[:S]), list(arrays[S:S + n]), list(arrays[S + n:])
+        loss5, unit = _run_loss(tgt, src, K, disps, poses, masks, cfg, grad)
+        terms = loss5[1:]
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)              # (no zero-filled gradient for `terms`: one fill kernel less per step)
+        ctx.save_for_backward(unit)                   # (freed by a backward without retain_graph, like any saved tensor)
+        ctx.grad = grad
+        ctx.spans, _ = _grad_spans(disps, poses, masks)
+        ctx.shapes = [a.shape for a in arrays]
+        return loss5[0], terms
+
+    @staticmethod
+    def backward(ctx, g_total, g_terms):
+        (unit,) = ctx.saved_tensors
+        if g_total is None or not ctx.grad:     # (not ctx.grad: only an image or the intrinsics required a gradient)
+            return (None,) * (7 + len(ctx.shapes))
+        return (None,) * 7 + tuple(_scaled(unit, ctx.spans, ctx.shapes, g_total.to(torch.float32)))
+
+
+def _dev_float(t, name, ndim=None):
+    """A differentiable network output: float32, bfloat16 or float16 on a ROCm device -> float32, contiguous (casts and copies are
+    recorded by autograd, so the gradient returns in the input's dtype and layout)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: expected a torch.Tensor on a ROCm device, got %s" % (name, type(t).__name__))
+    if not t.is_cuda:
+        raise TypeError("%s: CPU arrays are not supported by this build (GPU-only, no CPU fallback)" % name)
+    if t.dtype not in _FLOATS:
+        raise TypeError("%s: expected dtype float32, bfloat16 or float16, got %s" % (name, t.dtype))
+    if ndim is not None and t.dim() != ndim:
+        raise TypeError("%s: expected ndim == %d, got %d" % (name, ndim, t.dim()))
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _poses(pred_poses, B, n_src):
+    """A list of n_src (B,6) tensors (contiguous or not, e.g. h.split(6, 1)) or PoseNet's packed (B,6*n_src) output ->
+    n_src contiguous float32 (B,6) arrays."""
+    if isinstance(pred_poses, torch.Tensor):
+        packed = _dev_float(pred_poses, "pred_poses", 2)
+        if tuple(packed.shape) != (B, 6 * n_src):
+            raise TypeError("pred_poses: expected (B,6*n_src) = (%d,%d), got %s" % (B, 6 * n_src, tuple(packed.shape)))
+        return list(packed.view(B, n_src, 6).transpose(0, 1).contiguous().unbind(0))
+    poses = list(pred_poses)
+    if len(poses) != n_src:
+        raise TypeError("src_imgs has %d sources but %d poses were given" % (n_src, len(poses)))
+    out = []
+    for i, t in enumerate(poses):
+        t = _dev_float(t, "pred_poses[%d]" % i, 2)
+        if tuple(t.shape) != (B, 6):
+            raise TypeError("pred_poses[%d] must be (B,6) = (%d,6), got %s" % (i, B, tuple(t.shape)))
+        out.append(t)
+    return out
+
+
+def sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred_maskes=None, *, smooth_reg, exp_reg=0.,
+                     ssim_rate=0., smooth_mode="second_order", projection="fast", norm_batch=None):
+    """The loss of SFMLearner.__call__ (models/base_model.py:48-124) with torch.autograd gradients.
+
+    tgt_img (B,3,H,W) and src_imgs (B,n_src,3,H,W): float32 images; intrinsics (B,S,3,3) float32 -- constants, as the reference's
+      `.data` makes them (:71-72): no gradient flows to them.
+    pred_disps: S tensors (B,1,H>>s,W>>s); pred_poses: n_src tensors (B,6) (views such as h.split(6, 1) are fine) or one packed
+      (B,6*n_src) tensor; pred_maskes: S explainability logits (B,n_src,H>>s,W>>s), needed iff exp_reg > 0.  Float32, bfloat16 or
+      float16 (autocast) on a ROCm device: computed in float32, each gradient returned in its input's dtype.
+    smooth_mode: "second_order" (the reference's live form), "edge_aware" or "none"; projection: "fast" or "reference_order"
+      (include/sfmwarp.h); norm_batch: the global batch when this call holds a shard of it.
+
+    Returns (total_loss, terms): total_loss a 0-d tensor; terms = (pixel, smooth, exp, ssim), shape (4,).  The fused kernel
+    produces the gradient of total_loss only: `terms` is NOT differentiable (report it, do not backpropagate through it).
+
+    With grad mode on and any prediction requiring grad, ONE fused launch computes the loss and its gradients for gy = 1; backward
+    scales them by the upstream gradient on the device (so loss scaling, GradScaler and graph capture work, and no call syncs).
+    Gradients are per call: several forwards before one backward each keep their own."""
+    if smooth_mode not in _lib.SMOOTH_MODES:
+        raise ValueError("smooth_mode must be one of %s" % sorted(k for k in _lib.SMOOTH_MODES if k))
+    if projection not in _lib.PROJECTIONS:
+        raise ValueError("projection must be one of %s" % sorted(k for k in _lib.PROJECTIONS if k))
+    tgt = ops._dev(tgt_img, "tgt_img", 4)
+    src = ops._dev(src_imgs, "src_imgs", 5)
+    B, n_src, c, H, W = src.shape
+    if tuple(tgt.shape) != (B, 3, H, W) or c != 3:
+        raise TypeError("tgt_img must be (B,3,H,W) and src_imgs (B,n_src,3,H,W), got %s and %s" % (tuple(tgt.shape), tuple(src.shape)))
+    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d source images, got %d" % (_lib.SFM_MAX_SRC, n_src))
+    S = len(pred_disps)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
+    K = ops._dev(intrinsics, "intrinsics", 4)
+    if tuple(K.shape) != (B, S, 3, 3):
+        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
+    disps = []
+    for s, t in enumerate(pred_disps):
+        t = _dev_float(t, "pred_disps[%d]" % s, 4)
+        if tuple(t.shape) != (B, 1, H >> s, W >> s):
+            raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s, got %s" % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
+        disps.append(t)
+    poses = _poses(pred_poses, B, n_src)
+    exp_reg = float(exp_reg or 0.0)
+    masks = []
+    if exp_reg > 0:
+        if pred_maskes is None or len(pred_maskes) != S:
+            raise ValueError("exp_reg > 0 needs the explainability logits (pred_maskes), one per scale")
+        for s, t in enumerate(pred_maskes):
+            t = _dev_float(t, "pred_maskes[%d]" % s, 4)
+            if tuple(t.shape) != (B, n_src, H >> s, W >> s):
+                raise TypeError("pred_maskes[%d] must be (B,n_src,H>>%d,W>>%d), got %s" % (s, s, s, tuple(t.shape)))
+            masks.append(t)
+    for t in [K] + disps + poses + masks:
+        if t.device != tgt.device:
+            raise TypeError("every array must live on %s, one is on %s" % (tgt.device, t.device))
+    grad = torch.is_grad_enabled() and any(t.requires_grad for t in disps + poses + masks)
+    cfg = (float(smooth_reg or 0.0), exp_reg, float(ssim_rate or 0.0), _lib.SMOOTH_MODES[smooth_mode], _lib.PROJECTIONS[projection],
+           int(norm_batch if norm_batch is not None else B))
+    stacked = src.view(B, 3 * n_src, H, W)
+    if torch.compiler.is_compiling():
+        total, terms, _ = torch.ops.sfmwarp.sfm_learner_loss(tgt, stacked, K, disps, poses, masks, *cfg, grad)
+        return total, terms
+    return _LossFunction.apply(tgt, stacked, K, cfg, grad, S, n_src, *disps, *poses, *masks)
+
+
+class SFMLearnerLoss(torch.nn.Module):
+    """The loss half of the reference's SFMLearner link (models/base_model.py:28-124) as a torch.nn.Module: the constructor takes
+    the reference's config keys (smooth_reg, exp_reg, ssim_rate, seq_len), forward() the arguments of links.SFMLearnerLoss and
+    returns the total loss (0-d, differentiable).  `last_report` holds the five reported scalars of the latest call
+    (total_loss, pixel_loss, smooth_loss, exp_loss, ssim_loss: 0-d device tensors -- reading the dict does not sync)."""
+
+    def __init__(self, config, smooth_mode="second_order", projection="fast"):
+        super().__init__()
+        self.n_sources = config['seq_len'] - 1
+        self.smooth_reg = config['smooth_reg']
+        self.exp_reg = config['exp_reg']
+        self.ssim_rate = parse_dict(config, 'ssim_rate', 0.0)
+        self.smooth_mode = smooth_mode
+        self.projection = projection
+        self._last = None
+
+    def forward(self, tgt_img, src_imgs, intrinsics, inv_intrinsics, pred_disps, pred_poses, pred_maskes=None, norm_batch=None):
+        """inv_intrinsics is unused, as in the reference (base_model.py:48)."""
+        if isinstance(src_imgs, torch.Tensor) and src_imgs.dim() == 5 and src_imgs.shape[1] != self.n_sources:
+            raise TypeError("src_imgs has %d sources, the config's seq_len says %d" % (src_imgs.shape[1], self.n_sources))
+        total, terms = sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred_maskes,
+                                        smooth_reg=self.smooth_reg, exp_reg=self.exp_reg, ssim_rate=self.ssim_rate,
+                                        smooth_mode=self.smooth_mode, projection=self.projection, norm_batch=norm_batch)
+        self._last = (total.detach(), terms)
+        return total
+
+    @property
+    def last_report(self):
+        """{'total_loss', 'pixel_loss', 'smooth_loss', 'exp_loss', 'ssim_loss'} of the latest call (models/base_model.py:119-123):
+        0-d device tensors, None before the first call."""
+        if self._last is None:
+            return None
+        total, terms = self._last
+        return dict(zip(("total_loss", "pixel_loss", "smooth_loss", "exp_loss", "ssim_loss"), (total,) + tuple(terms.unbind(0))))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# operators
+# ---------------------------------------------------------------------------------------------------------------------------
+class _Warp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, imgs, depthes, poses, K):
+        ctx.save_for_backward(imgs, depthes, poses, K)
+        return ops.warp_fwd(imgs, depthes, poses, K)
+
+    @staticmethod
+    def backward(ctx, g):
+        imgs, depthes, poses, K = ctx.saved_tensors
+        d_depth, d_pose, d_src = ops.warp_bwd(imgs, depthes, poses, K, g.contiguous(), want_d_src=ctx.needs_input_grad[0])
+        return d_src, d_depth.view(depthes.shape), d_pose, None
+
+
+def projective_inverse_warp(imgs, depthes, poses, K):
+    """models/transform.py:156-193: imgs (N,C,H,W), depthes (N,3,H*W) or (N,H*W), poses (N,6), K (N,3,3), float32 on a ROCm
+    device -> the warped images (N,C,H,W).  Gradients flow to imgs, depthes and poses (ops.warp_bwd), not to K."""
+    return _Warp.apply(imgs, depthes, poses, K)
+
+
+class _DispAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, *xs):
+        outs = ops.disp_act_fwd(xs)
+        ctx.save_for_backward(*outs)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        return tuple(ops.disp_act_bwd(ctx.saved_tensors, [g.contiguous() for g in gs]))
+
+
+def disp_activation(xs):
+    """DispNet's output activation, models/disp_net.py:104-122: [10 * sigmoid(x) + 0.01 for x in xs], all scales in one launch
+    (ops.disp_act_fwd; backward ops.disp_act_bwd).  float32, bfloat16 or float16 on a ROCm device (the logits of a network under
+    autocast): computed and returned in float32, each gradient returned in its input's dtype."""
+    return list(_DispAct.apply(*[_dev_float(x, "xs[%d]" % k) for k, x in enumerate(xs)]))
