@@ -7,6 +7,14 @@
  *
  *   - all tensors are float32, C-contiguous, NCHW, resident in device (HBM) memory and owned
  *     by the caller; the library never allocates, frees or keeps a pointer after return;
+ *   - alignment: 4 bytes (that of a float) suffices for every tensor, input or output, each scale and each pose on its own -- a
+ *     contiguous view into a larger array (a batch shard `a[lo:hi]`) is as good as an allocation of its own, with the same results
+ *     bit for bit; where a kernel has a 16-byte path it tests the addresses itself.  The one exception is the scratch `ws` of
+ *     sfm_loss_* / sfm_step_*: 256 bytes (see there);
+ *   - memory written: an output marked "overwritten" is written completely, whatever it held (it is never read); one marked
+ *     ACCUMULATED is added to; inputs are only read; scratch (`ws`) may hold anything before the call and holds nothing of use
+ *     after it -- no result depends on its previous content; nothing outside the outputs and `ws_bytes` of `ws` is written.  A call
+ *     that returns SFM_ERR_* has launched nothing and written nothing;
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); every call is
  *     asynchronous with respect to the host, re-entrant, and keeps no global mutable state
  *     (the reference's module globals `filler` / `meshgrid`, models/transform.py:62,135, are
@@ -41,7 +49,7 @@ extern "C" {
 #define SFM_ERR_NULL (-1)      /* a required pointer is NULL                       */
 #define SFM_ERR_SHAPE (-2)     /* a dimension is out of the supported range        */
 #define SFM_ERR_CONFIG (-3)    /* inconsistent loss configuration                  */
-#define SFM_ERR_WORKSPACE (-4) /* workspace missing or too small                   */
+#define SFM_ERR_WORKSPACE (-4) /* workspace missing, too small or misaligned         */
 
 #define SFM_MAX_SCALES 8
 #define SFM_MAX_SRC 8
@@ -71,7 +79,7 @@ int sfm_pose_proj_bwd(const float *pose6, const float *K, const float *g_proj, f
  *   d_depth (N,depth_rows,H*W) overwritten
  *   d_pose6 (N,6)     overwritten
  *   d_src   (N,C,H,W) or NULL; ACCUMULATED into (zero it first) with float atomics
- *   ws: sfm_warp_bwd_workspace_bytes(N,H,W) bytes of scratch.
+ *   ws: sfm_warp_bwd_workspace_bytes(N,H,W) bytes of scratch (4-byte aligned; fewer bytes: SFM_ERR_WORKSPACE).
  * H, W >= 3 (below that the reference's x2 rule no longer implies zero fill).
  * ---------------------------------------------------------------------------------------- */
 int sfm_warp_fwd(const float *src, const float *depth, int depth_rows, const float *pose6, const float *K,
@@ -179,8 +187,12 @@ typedef struct SfmLossDesc {
   int32_t projection;            /* SFM_PROJECTION_* (ABI v5); 0 = SFM_PROJECTION_FAST        */
 } SfmLossDesc;
 
-/* scratch needed by the three calls below for this descriptor (0 on a bad descriptor).  It depends on the shapes, on n_src and on
- * WHICH d_src[] are bound: query with the descriptor the calls will get. */
+/* scratch needed by the three calls below for this descriptor (0 on a bad descriptor; a multiple of 256).  It depends on the shapes,
+ * on n_src and on WHICH d_src[] are bound: query with the descriptor the calls will get.
+ * `ws` of sfm_loss_* and sfm_step_*: at least that many bytes (`ws_bytes` says how many), starting on a 256-BYTE boundary -- the
+ * per-wavefront partial sums are laid out in it in 256-byte aligned arrays of 16- and 48-byte records that are read back 16 bytes at
+ * a time.  ws NULL, ws_bytes too small or ws off the boundary: SFM_ERR_WORKSPACE before anything is launched.  Its content is
+ * undefined before and after a call; two calls in flight at the same time (two streams) need a workspace each. */
 size_t sfm_loss_workspace_bytes(const SfmLossDesc *desc);
 
 /* loss5 (device, 5 floats): total, pixel, smooth, exp, ssim -- the chainer.report keys
@@ -244,7 +256,8 @@ int sfm_pyramid_pair_hwc_fwd(const float *tgt, const float *src, float *const *y
  * desc->src[s], which the descriptor must bind as SFM_LAYOUT_HWC with H[s] = H[0] >> s, W[s] = W[0] >> s -- followed by
  * sfm_loss_fwd (sfm_step_fwd) or sfm_loss_fwd_bwd (sfm_step_fwd_bwd) on the same stream.  Exactly the two calls it replaces, same
  * results bit for bit; it exists for callers whose step is host-bound (the reference trains at B = 4, experiments/sfm_learner_v1.yml:43:
- * 25 us of GPU work per step): one trip through the FFI, one argument conversion, one plan look-up. */
+ * 25 us of GPU work per step): one trip through the FFI, one argument conversion, one plan look-up.  Every argument -- descriptor,
+ * loss5, workspace -- is checked BEFORE the pyramids are written: a rejected step leaves desc->tgt[] / desc->src[] as they were. */
 int sfm_step_fwd(const float *tgt_full, const float *src_full, const SfmLossDesc *desc, float *loss5, void *ws, size_t ws_bytes,
                  void *stream);
 int sfm_step_fwd_bwd(const float *tgt_full, const float *src_full, const SfmLossDesc *desc, float *loss5, void *ws, size_t ws_bytes,

@@ -803,8 +803,10 @@ static int cached_plan(const SfmLossDesc* d, bool grad, bool loss, float gy, Pla
   return SFM_OK;
 }
 
+// `tgt_full` / `src_full` (sfm_step_*): the full-resolution frames whose pyramids are written into d->tgt[] / d->src[] first -- after
+// every argument of the call has been checked, so that a rejected call has launched nothing and written nothing.
 static int run(const SfmLossDesc* d, bool grad, bool loss, float gy, float* loss5, void* ws, size_t ws_bytes, void* stream,
-               const char* who) {
+               const char* who, const float* tgt_full = nullptr, const float* src_full = nullptr, bool from_frames = false) {
   hipStream_t st = (hipStream_t)stream;
   // the one-call hooks are taken -- and forgotten -- here, whatever becomes of the call
   const int variant = g_variant;
@@ -828,6 +830,10 @@ static int run(const SfmLossDesc* d, bool grad, bool loss, float gy, float* loss
   if (loss && !loss5) return fail(SFM_ERR_NULL, "%s: loss5 is NULL", who);
   if (!ws || ws_bytes < p.total) return fail(SFM_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, got %zu", who, p.total, ws_bytes);
   if (((uintptr_t)ws & 255) != 0) return fail(SFM_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+  if (from_frames)
+    if (int e = sfm_pyramid_pair_hwc_fwd(tgt_full, src_full, (float* const*)d->tgt, (float* const*)d->src, d->B, d->n_src, d->H[0], d->W[0],
+                                         d->n_scales, stream))
+      return e;
   bind_workspace(p, ws);
   p.args.trace = trace;
   hipError_t le;
@@ -925,11 +931,11 @@ static int step_from_frames(const float* tgt_full, const float* src_full, const 
     if (d->H[s] != d->H[0] >> s || d->W[s] != d->W[0] >> s)
       return sfm::fail(SFM_ERR_SHAPE, "%s: scale %d is %dx%d, the pyramid of a %dx%d frame has %dx%d there (base_model.py:70)", who, s, d->H[s],
                        d->W[s], d->H[0], d->W[0], d->H[0] >> s, d->W[0] >> s);
-  // (the descriptor's pyramid pointers are inputs of the loss and outputs of this call: the caller owns the buffers either way)
-  if (int e = sfm_pyramid_pair_hwc_fwd(tgt_full, src_full, (float* const*)d->tgt, (float* const*)d->src, d->B, d->n_src, d->H[0], d->W[0],
-                                       d->n_scales, stream))
-    return e;
-  return sfm::run(d, grad, true, 1.f, loss5, ws, ws_bytes, stream, who);
+  // (the descriptor's pyramid pointers are inputs of the loss and outputs of this call: the caller owns the buffers either way.
+  //  sfm::run writes the pyramids -- sfm_pyramid_pair_hwc_fwd -- once it has accepted the descriptor, loss5 and the workspace)
+  const int rc = sfm::run(d, grad, true, 1.f, loss5, ws, ws_bytes, stream, who, tgt_full, src_full, true);
+  if (rc < 0) sfm_pyramid_variant(0);      // a rejected step has consumed the one-call pyramid hook too, like a rejected pyramid call
+  return rc;
 }
 
 int sfm_step_fwd(const float* tgt_full, const float* src_full, const SfmLossDesc* desc, float* loss5, void* ws, size_t ws_bytes, void* stream) {

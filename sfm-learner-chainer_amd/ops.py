@@ -308,11 +308,16 @@ class FusedLoss:
         self._keep = None
 
     def bind(self, tgt_pyr, src_pyr, intrinsics, disps, poses, masks=None, norm_B=None, want_d_src=False, layout="planar",
-             want_warped=False):
+             want_warped=False, buffers=None):
         """layout: "planar" -- tgt (B,3,h,w), src (B,3*n_src,h,w) as in the reference; "hwc" -- tgt (B,1,h,w,3),
         src (B,n_src,h,w,3) as written by `pyramid_hwc` (the faster layout for these kernels; same results).
         want_warped: `forward` / `forward_backward` also write `self.warped[s]` (B,n_src,3,h,w), the warped source images the
-        loss was computed on (curr_proj_img, models/base_model.py:90-94; planar in both layouts)."""
+        loss was computed on (curr_proj_img, models/base_model.py:90-94; planar in both layouts).
+        buffers: optional dict of caller-owned arrays to use instead of allocating -- any of "d_disps", "d_poses", "d_masks",
+        "warped" (lists, one array per scale / source), "d_srcs" (one array or None per scale: replaces `want_d_src`; the caller's
+        arrays are cleared before every backward like the own ones), "loss5" ((5,) float32) and "ws" (a contiguous device tensor of
+        any dtype that starts on a 256-byte boundary; ALL its bytes are handed over as the workspace, and it must hold at least
+        sfm_loss_workspace_bytes).  Float arrays need the shapes given above and 4-byte alignment, nothing more."""
         if layout not in ("planar", "hwc"):
             raise ValueError("layout must be 'planar' or 'hwc', got %r" % (layout,))
         hwc = layout == "hwc"
@@ -343,11 +348,26 @@ class FusedLoss:
         d.image_layout = _lib.SFM_LAYOUT_HWC if hwc else _lib.SFM_LAYOUT_PLANAR
         d.projection = self.projection
         d_disps, d_masks, d_srcs, warped = [], [], [], []
+        buffers = dict(buffers or {})
+
+        def own(key, k, shape):
+            """the caller's array `buffers[key][k]` if it gave one, else a fresh one"""
+            if buffers.get(key) is None:
+                return torch.empty(shape, dtype=torch.float32, device=dev)
+            t = buffers[key] if key == "loss5" else buffers[key][k]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
+                    or tuple(t.shape) != tuple(shape):
+                raise TypeError("buffers[%r][%d]: expected a contiguous float32 array of shape %s on %s" % (key, k, tuple(shape), dev))
+            return t
+
+        given_src = buffers.get("d_srcs")
+        if given_src is not None:
+            want_d_src = [t is not None for t in given_src]
         # the d_src arrays of all bound scales are views of ONE allocation: the library accumulates into them (float atomics), so every
         # backward starts by clearing them -- one fill kernel instead of one per scale
         want_src = [bool(want_d_src[s] if isinstance(want_d_src, (list, tuple)) else want_d_src) for s in range(S)]
         src_numel = [B * 3 * n_src * int(disps[s].shape[2]) * int(disps[s].shape[3]) if want_src[s] else 0 for s in range(S)]
-        self._d_src_all = torch.zeros((sum(src_numel),), dtype=torch.float32, device=dev) if any(want_src) else None
+        self._d_src_all = torch.zeros((sum(src_numel),), dtype=torch.float32, device=dev) if any(want_src) and given_src is None else None
         src_off = 0
         for s in range(S):
             h, w = disps[s].shape[2:]
@@ -360,40 +380,55 @@ class FusedLoss:
                                 "disp (B,1,h,w)" % s)
             d.H[s], d.W[s] = h, w
             d.tgt[s], d.src[s], d.disp[s] = tgt_pyr[s].data_ptr(), src_pyr[s].data_ptr(), disps[s].data_ptr()
-            d_disps.append(torch.empty_like(disps[s]))
+            d_disps.append(own("d_disps", s, disps[s].shape))
             d.d_disp[s] = d_disps[-1].data_ptr()
             if use_masks:
                 if tuple(masks[s].shape) != (B, n_src, h, w):
                     raise TypeError("masks[%d] must be (B,n_src,h,w)" % s)
                 d.mask_logits[s] = masks[s].data_ptr()
-                d_masks.append(torch.empty_like(masks[s]))
+                d_masks.append(own("d_masks", s, masks[s].shape))
                 d.d_mask[s] = d_masks[-1].data_ptr()
             # (want_d_src: True, or one flag per scale -- SfmLossDesc.d_src[s] may be NULL for any scale)
-            if want_src[s]:      # always planar
+            if want_src[s] and given_src is not None:
+                d_srcs.append(own("d_srcs", s, (B, 3 * n_src, h, w)))
+                d.d_src[s] = d_srcs[-1].data_ptr()
+            elif want_src[s]:      # always planar
                 d_srcs.append(self._d_src_all[src_off:src_off + src_numel[s]].view(B, 3 * n_src, h, w))
                 src_off += src_numel[s]
                 d.d_src[s] = d_srcs[-1].data_ptr()
             else:
                 d_srcs.append(None)
             if want_warped:     # always planar
-                warped.append(torch.empty((B, n_src, 3, h, w), dtype=torch.float32, device=dev))
+                warped.append(own("warped", s, (B, n_src, 3, h, w)))
                 d.warped[s] = warped[-1].data_ptr()
         d_poses = []
         for i in range(n_src):
             if tuple(poses[i].shape) != (B, 6):
                 raise TypeError("poses[%d] must be (B,6)" % i)
             d.pose[i] = poses[i].data_ptr()
-            d_poses.append(torch.empty_like(poses[i]))
+            d_poses.append(own("d_poses", i, poses[i].shape))
             d.d_pose[i] = d_poses[-1].data_ptr()
         nbytes = lib.sfm_loss_workspace_bytes(C.byref(d)) if B > 0 else 256
         if nbytes == 0:
             check(lib.sfm_loss_fwd(C.byref(d), None, None, 0, None))   # re-run the validation for its message
             raise ValueError(_lib.last_error() or "invalid loss descriptor")
-        self.ws = torch.empty((nbytes // 4 + 64,), dtype=torch.float32, device=dev)
-        off = (-self.ws.data_ptr()) % 256
-        self._ws_ptr = self.ws.data_ptr() + off
-        self._ws_bytes = nbytes
-        self.loss5 = torch.zeros((5,), dtype=torch.float32, device=dev)
+        # the workspace as include/sfmwarp.h states it: sfm_loss_workspace_bytes bytes on a 256-byte boundary, content undefined
+        # (a fresh torch allocation starts on a 512-byte boundary; should an allocator ever hand out less, 256 spare bytes absorb it)
+        if buffers.get("ws") is not None:
+            self.ws = buffers["ws"]
+            if not isinstance(self.ws, torch.Tensor) or self.ws.device != dev or not self.ws.is_contiguous():
+                raise TypeError("buffers['ws']: expected a contiguous tensor on %s" % (dev,))
+            self._ws_ptr, self._ws_bytes = self.ws.data_ptr(), self.ws.numel() * self.ws.element_size()
+            if self._ws_ptr % 256 or self._ws_bytes < nbytes:
+                raise ValueError("buffers['ws']: need %d bytes on a 256-byte boundary, got %d bytes at offset %d mod 256"
+                                 % (nbytes, self._ws_bytes, self._ws_ptr % 256))
+        else:
+            self.ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            if self.ws.data_ptr() % 256:
+                self.ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
+            self._ws_ptr = self.ws.data_ptr() + (-self.ws.data_ptr()) % 256
+            self._ws_bytes = nbytes
+        self.loss5 = torch.zeros((5,), dtype=torch.float32, device=dev) if buffers.get("loss5") is None else own("loss5", 0, (5,))
         self.desc, self.device = d, dev
         self._desc_ref, self._ws_arg, self._loss5_arg = C.byref(d), C.c_void_p(self._ws_ptr), _p(self.loss5)
         self.d_disps, self.d_poses, self.d_masks, self.d_srcs = d_disps, d_poses, (d_masks if use_masks else None), \
@@ -433,8 +468,14 @@ class FusedLoss:
         return self
 
     def _zero_d_src(self):
-        if self.d_srcs is not None:
+        if self.d_srcs is None:
+            return
+        if self._d_src_all is not None:
             self._d_src_all.zero_()
+        else:      # the caller's arrays (bind(buffers=...)): one fill each
+            for t in self.d_srcs:
+                if t is not None:
+                    t.zero_()
 
     def _launch(self, fn, *mid):
         """One call through the C ABI on the device's current stream.  The argument objects that never change between

@@ -131,6 +131,46 @@ def test_missing_workspace_is_reported_before_any_launch():
     assert rc == _lib.ERR_WORKSPACE and "workspace" in _lib.last_error()
 
 
+def _call(entry, d, loss5, ws, ws_bytes):
+    L = _lib.lib
+    fake = C.c_void_p(0x1000)
+    if entry == "sfm_loss_bwd":
+        return L.sfm_loss_bwd(C.byref(d), 1.0, ws, ws_bytes, None)
+    if entry.startswith("sfm_step"):
+        return getattr(L, entry)(fake, fake, C.byref(d), loss5, ws, ws_bytes, None)
+    return getattr(L, entry)(C.byref(d), loss5, ws, ws_bytes, None)
+
+
+@pytest.mark.parametrize("entry", ["sfm_loss_fwd", "sfm_loss_bwd", "sfm_loss_fwd_bwd", "sfm_step_fwd", "sfm_step_fwd_bwd"])
+def test_short_or_misaligned_workspace_is_rejected_before_any_launch(entry):
+    """include/sfmwarp.h: `ws` holds at least sfm_loss_workspace_bytes(desc) bytes and starts on a 256-byte boundary.  One byte
+    short, or 4 / 128 bytes off the boundary: SFM_ERR_WORKSPACE with a message, from every entry point, before anything is launched
+    (no device here: a launch would fail with a positive code instead).  sfm_step_* reject before they write the pyramids, too."""
+    d = _desc(ssim_rate=0.15, smooth_reg=0.1, smooth_mode=_lib.SMOOTH_SECOND_ORDER, image_layout=_lib.SFM_LAYOUT_HWC)
+    for s in range(2):
+        d.d_disp[s] = 0x1000
+    d.d_pose[0] = d.d_pose[1] = 0x1000
+    n = _lib.lib.sfm_loss_workspace_bytes(C.byref(d))
+    assert n > 0 and n % 256 == 0
+    buf = (C.c_float * 5)()
+    loss5 = C.cast(buf, C.c_void_p)
+    for ws, ws_bytes, word in ((0x10000, n - 1, "needed"), (0x10004, n, "aligned"), (0x10080, n, "aligned"), (0x10004, n + 4096, "aligned"),
+                               (None, n, "needed")):
+        rc = _call(entry, d, loss5, C.c_void_p(ws) if ws else None, ws_bytes)
+        assert rc == _lib.ERR_WORKSPACE, (entry, ws, ws_bytes, rc, _lib.last_error())
+        assert "workspace" in _lib.last_error() and word in _lib.last_error(), _lib.last_error()
+        with pytest.raises(ValueError):
+            _lib.check(rc)
+
+
+def test_warp_bwd_workspace_one_byte_short_is_rejected():
+    fake = C.c_void_p(0x1000)
+    n = _lib.lib.sfm_warp_bwd_workspace_bytes(2, 16, 24)
+    rc = _lib.lib.sfm_warp_bwd(fake, fake, 1, fake, fake, fake, fake, fake, None, fake, n - 1, 2, 3, 16, 24, None)
+    assert rc == _lib.ERR_WORKSPACE and "workspace" in _lib.last_error()
+    assert _lib.lib.sfm_warp_bwd(fake, fake, 1, fake, fake, fake, fake, fake, None, None, n, 2, 3, 16, 24, None) == _lib.ERR_WORKSPACE
+
+
 def test_operator_argument_errors_need_no_gpu():
     L = _lib.lib
     assert L.sfm_warp_fwd(None, None, 1, None, None, None, 1, 3, 8, 8, None) == _lib.ERR_NULL
