@@ -210,8 +210,10 @@ int sfm_loss_fwd_bwd(const SfmLossDesc *desc, float *loss5, void *ws, size_t ws_
 int sfm_loss_profile_events(void *ev_start, void *ev_stop);
 /* Host-side only (no device needed): the work decomposition the library chooses for `desc` and the entry point given by
  * (grad, loss) = (0,1) sfm_loss_fwd, (1,0) sfm_loss_bwd, (1,1) sfm_loss_fwd_bwd.  out[0] = wavefront items of the launch; then
- * per scale four ints: strips, row chunks per strip, rows of a chunk, items per sample (n_out >= 1 + 4 * n_scales).  For tests
- * and tuning; nothing is launched. */
+ * per scale four ints: strips, row chunks per strip, rows of a chunk, items per sample (n_out >= 1 + 4 * n_scales).  With
+ * n_out >= 1 + 4 * n_scales + 2 two more ints follow: the kernel family of the main launch (0 base, 1 the three-waves-per-SIMD build
+ * of the small L1 gradient launches, 2 two sources per pass, 3 reference-order projection, 4 the kernels that record dL/dI^ for d_src)
+ * and its resident waves per SIMD.  For tests and tuning; nothing is launched. */
 int sfm_loss_plan_info(const SfmLossDesc *desc, int grad, int loss, int *out, int n_out);
 
 /* Development / test hook, consumed by the NEXT sfm_loss_* call of the calling thread (whatever becomes of that call), then back

@@ -55,7 +55,7 @@ constexpr int FINALIZE_WAVES = 16;   // waves of the block that sums the loss pa
 //   q_bsc: B | n_src << 16 | n_scales << 20 | COMPACT << 24 | POSE << 25 | LOSS << 26;  q_t01 .. q_t67: tiles_of[] as 16-bit halves;
 //   q_loss_back: bytes from part_loss up to part_gpm (both lie in the caller's workspace: the loss block's pointer without a round trip).
 // COMPACT = 0 (a tile count or B beyond 16 bits: planar frames of tens of megapixels): the fields are read from the struct, as before.
-constexpr unsigned FIN_COMPACT = 1u << 24, FIN_POSE = 1u << 25, FIN_LOSS = 1u << 26;
+// (FIN_* and the HDR_* field positions: sfm_loss_kernels.h, next to make_hdr)
 __global__ void __launch_bounds__(64 * FINALIZE_WAVES) finalize_kernel(const float* __restrict__ q_gpm, const float* __restrict__ q_intr,
                                                                        const float* __restrict__ q_pose0, const float* __restrict__ q_pose1,
                                                                        const unsigned q_bsc, const unsigned q_t01, const unsigned q_t23,
@@ -67,13 +67,13 @@ __global__ void __launch_bounds__(64 * FINALIZE_WAVES) finalize_kernel(const flo
   int hB, h_src, h_scales, h_items, tlh[SFM_MAX_SCALES], ibh[SFM_MAX_SCALES];
   const float *h_gpm, *h_intr, *h_loss;
   if (compact) {          // (uniform)
-    hB = (int)(q_bsc & 0xffffu); h_src = (int)((q_bsc >> 16) & 0xfu); h_scales = (int)((q_bsc >> 20) & 0xfu);
+    hB = (int)(q_bsc & HDR_B_MASK); h_src = (int)((q_bsc >> HDR_SRC_SHIFT) & HDR_NIBBLE); h_scales = (int)((q_bsc >> HDR_SCALES_SHIFT) & HDR_NIBBLE);
     const unsigned tw[4] = {q_t01, q_t23, q_t45, q_t67};
     int run = 0;
 #pragma unroll
     for (int k = 0; k < SFM_MAX_SCALES; ++k) {
-      tlh[k] = (int)((tw[k >> 1] >> (16 * (k & 1))) & 0xffffu);
-      ibh[k] = run;                              // make_plan: item_begin of a scale = B x the tiles of the scales before it
+      tlh[k] = (int)((tw[hdr_tile_word(k)] >> hdr_tile_shift(k)) & HDR_TILE_MASK);
+      ibh[k] = run;                              // plan_items: item_begin of a scale = B x the tiles of the scales before it
       run += hB * tlh[k];
     }
     h_items = run;
@@ -315,38 +315,47 @@ __global__ void __launch_bounds__(64 * FINALIZE_WAVES) finalize_kernel(const flo
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// The preloaded launch header of both launches (make_hdr, finalize_kernel), packed once, when the plan is made.
+struct PackedHdr {
+  bool compact;        // false (a tile count or B beyond 16 bits): the kernels read the fields from the struct
+  unsigned bsc;        // B | n_src << 16 | n_scales << 20
+  unsigned tiles[4];   // tiles_of[] as 16-bit halves
+};
+
 struct Plan {
   LossArgs args;
   size_t off_loss, off_gpm, total;
   size_t off_rec[SFM_MAX_SCALES];   // with d_src bound: the record of dL/dI^ of the scale (B, 3 n_src, h, w) that the second launch reads
   DsrcArgs dsrc_args;               // ... and that launch (dsrc_scatter_kernel, sfm_loss_dsrc.hip)
-  bool ssim, expl, hwc;
-  bool wide;     // the three-waves-per-SIMD build of an L1 gradient kernel (see loss_kernel)
-  bool pair;     // two sources per pass at two waves per SIMD (loss_kernel_pair, sfm_ssim_pair.h)
-  bool ref;      // SfmLossDesc.projection = SFM_PROJECTION_REFERENCE_ORDER: the kernels of sfm_loss_ref.hip
-  bool dsrc;     // the call also produces dL/d(src): the instantiations that record dL/dI^, and the second launch
-  bool warped;   // the instantiation that also writes SfmLossDesc.warped
-  int smode;
+  Variant v;                        // the main kernel (choose_variant)
+  const void* kernel;               // ... its __global__, resolved here so that a cached plan launches without another look-up
+  bool dsrc;                        // the CALL also produces dL/d(src): the main launch records dL/dI^ and a second launch follows
+  PackedHdr hdr;
 };
+
+struct Entry { bool grad, loss; };          // the entry point: sfm_loss_fwd {0, 1}, sfm_loss_bwd {1, 0}, sfm_loss_fwd_bwd {1, 1}
+enum class Outputs { Unchecked, Checked };  // Checked: a call that writes them (the queries plan from the descriptor's shape alone)
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// optional profiling hook (sfm_loss_profile_events): events recorded right before / after the
-// main kernel of the NEXT fused-loss call of this thread
-static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
-static thread_local unsigned long long* g_trace = nullptr;   // sfm_loss_debug_trace
-static thread_local int g_variant = 0;                       // sfm_loss_variant: holds for the next sfm_loss_* call only
+// The one-call hooks of the calling thread: they hold for the NEXT sfm_loss_* call only, whatever becomes of it.
+constexpr int HOOK_STRUCT_HEADER = 3;   // sfm_loss_variant: the header read from the struct (the path of counts beyond 16 bits)
+constexpr int HOOK_ONE_SOURCE = 4, HOOK_TWO_SOURCES = 5;   // ... one source per pass / two where possible, whatever the default
+struct Hooks {
+  int variant;                      // sfm_loss_variant
+  unsigned long long* trace;        // sfm_loss_debug_trace
+  hipEvent_t ev_start, ev_stop;     // sfm_loss_profile_events: recorded right before / after the main kernel
+};
+static thread_local Hooks g_hooks = {};
+static int pair_hook_of(const int variant) { return variant == HOOK_ONE_SOURCE ? 0 : (variant == HOOK_TWO_SOURCES ? 1 : -1); }
 
 // ---- work decomposition -----------------------------------------------------------------
 // One wavefront per (scale, sample, strip, chunk of rows).  A wave lives for the whole launch, so the chunk
 // height is chosen such that all items fit in as few full "rounds" of resident waves as possible while the
 // halo rows (recomputed per chunk) stay a small fraction.  The number of resident waves follows from the
-// __launch_bounds__ of the kernel variant (3 waves per SIMD for the SSIM gradient kernels, 4 otherwise; LDS
-// and the 32-waves-per-CU cap allow more) and from the CU count of the device -- no occupancy query, nothing
-// that differs between a CPU-only host and the GPU box.
-template <bool GRAD, bool LOSS>
-static const void* kernel_ptr(bool ssim, bool expl, int smode, bool hwc, bool wide, bool warped);
-
+// __launch_bounds__ of the kernel variant (waves_per_simd; LDS and the 32-waves-per-CU cap allow more) and
+// from the CU count of the device -- no occupancy query, nothing that differs between a CPU-only host and
+// the GPU box.
 constexpr int MI355X_CUS = 256;   // 8 XCDs x 32 CUs (MI355X_MICROARCH.md); used when no device is visible
 
 static int device_cus() {
@@ -361,12 +370,6 @@ static int device_cus() {
   return cus_of[dev];
 }
 
-static int waves_per_simd_of(bool ssim, bool grad, bool wide, bool dsrc, bool pair) {   // = __launch_bounds__ of the kernel
-  if (pair) return 2;
-  (void)dsrc;    // (the kernels that record dL/dI^ for dL/d(src) run at the occupancy of the others)
-  return ((ssim && grad) || wide) ? 3 : 4;
-}
-
 // tuning overrides (development only), read from the environment ONCE per process
 struct Tuning {
   int chunk_rows = 0;                       // SFM_CHUNK_ROWS: fixed target height
@@ -374,7 +377,7 @@ struct Tuning {
   bool has_prio = false;
   unsigned prio_tab = 0;                    // SFM_PRIO_TABLE: "0123,3210" = levels of ranks 0.. in phase 1, phase 2
   bool no_wide = false;                     // SFM_NO_WIDE: small L1 launches on the four-wave build too
-  int pair = -1;                            // SFM_PAIR=0 / 1: never / whenever possible two sources per pass (default: make_plan decides)
+  int pair = -1;                            // SFM_PAIR=0 / 1: never / whenever possible two sources per pass (default: choose_variant decides)
   bool no_fill = false;                     // SFM_NO_FILL: no slot-filling refinement of the chunk heights (plan_chunks)
   int deal_below = 8;                       // SFM_DEAL_ITEMS_BELOW: batches smaller than this have their ITEMS dealt out over the XCDs (8 contiguous
                                             // ranges of the item list) instead of whole samples (b mod 8).  Measured at B = 8 (9): cfg5_2src +9.9 %,
@@ -486,13 +489,11 @@ static long long max_items(const SfmLossDesc* d, int sw) {
   return items;
 }
 
-static void set_gy(struct Plan& p, const float gy);
-static void plan_dsrc(const SfmLossDesc* d, const int cus, struct Plan& p);
+constexpr int PAIR_BELOW_ROWS = 12;   // see choose_variant
 
-constexpr int PAIR_BELOW_ROWS = 12;   // see make_plan
-
-// validates the descriptor and lays out items + workspace for the given mode
-static int make_plan(const SfmLossDesc* d, bool grad, bool need_loss, bool need_outputs, float gy, Plan& p, const int pair_hook = -1) {
+// ---- the plan, in stages ----------------------------------------------------------------
+// what a descriptor must satisfy whatever the entry point; the output arrays are left to validate_outputs
+static int validate(const SfmLossDesc* d) {
   if (!d) return fail(SFM_ERR_NULL, "sfm_loss: NULL descriptor");
   if (d->B < 0 || d->B > (1 << 20)) return fail(SFM_ERR_SHAPE, "sfm_loss: B=%d", d->B);
   if (d->norm_B < d->B || d->norm_B < 1) return fail(SFM_ERR_CONFIG, "sfm_loss: norm_B=%d must be >= max(B,1) (B=%d)", d->norm_B, d->B);
@@ -506,111 +507,123 @@ static int make_plan(const SfmLossDesc* d, bool grad, bool need_loss, bool need_
   if (!d->intrinsics) return fail(SFM_ERR_NULL, "sfm_loss: intrinsics is NULL");
   if (d->image_layout != SFM_LAYOUT_PLANAR && d->image_layout != SFM_LAYOUT_HWC)
     return fail(SFM_ERR_CONFIG, "sfm_loss: image_layout=%d", d->image_layout);
-  p.hwc = d->image_layout == SFM_LAYOUT_HWC;
   if (d->projection != SFM_PROJECTION_FAST && d->projection != SFM_PROJECTION_REFERENCE_ORDER)
     return fail(SFM_ERR_CONFIG, "sfm_loss: projection=%d", d->projection);
-  p.ref = d->projection == SFM_PROJECTION_REFERENCE_ORDER;
-  p.expl = d->exp_reg > 0.f;                       // base_model.py:86,103
-  p.ssim = !p.expl && d->ssim_rate > 0.f;          // base_model.py:110-112
-  p.smode = d->smooth_reg > 0.f ? d->smooth_mode : SFM_SMOOTH_NONE;   // base_model.py:75
-  LossArgs& A = p.args;
-  memset(&A, 0, sizeof(A));
-  A.B = d->B;
-  A.n_src = d->n_src;
-  A.n_scales = d->n_scales;
-  A.gy = gy;
-  A.alpha = d->ssim_rate;
-  A.intrinsics = d->intrinsics;
-  for (int i = 0; i < d->n_src; ++i) {
+  for (int i = 0; i < d->n_src; ++i)
     if (!d->pose[i]) return fail(SFM_ERR_NULL, "sfm_loss: pose[%d] is NULL", i);
-    A.pose[i] = d->pose[i];
-    if (grad && need_outputs) {
-      if (!d->d_pose[i]) return fail(SFM_ERR_NULL, "sfm_loss: d_pose[%d] is NULL", i);
-      A.d_pose[i] = d->d_pose[i];
-    }
-  }
-  // the optional warped-image output: an array for every scale or for none.  Which kernel runs follows from the descriptor's
-  // pointers whatever need_outputs says, so that sfm_loss_plan_info reports the launch the call will make; only the
-  // validation of the output arrays is left to the calls that write them.
-  p.warped = false;
-  if (need_loss) {
-    int n_w = 0;
-    for (int s = 0; s < d->n_scales; ++s) n_w += d->warped[s] != nullptr;
-    if (need_outputs && n_w != 0 && n_w != d->n_scales)
-      return fail(SFM_ERR_NULL, "sfm_loss: warped[] is set for %d of %d scales (all or none)", n_w, d->n_scales);
-    p.warped = n_w != 0;
-  }
-  const int sw = strip_width(p.ssim, grad, p.smode);
-  const int hs = p.ssim ? (grad ? 2 : 1) : 0;
-  const int hm = p.smode == 1 ? 2 : (p.smode == 2 ? 1 : 0);
-  int rows[SFM_MAX_SCALES];
-  for (int s = 0; s < d->n_scales; ++s)
-    if (d->H[s] < 3 || d->W[s] < 3) return fail(SFM_ERR_SHAPE, "sfm_loss: scale %d is %dx%d, need H,W >= 3", s, d->H[s], d->W[s]);
-  const int cus = device_cus();
-  // (a launch is "small" when even at the smallest chunk height its waves fit the SIMDs three deep)
-  p.dsrc = false;
-  if (grad)
-    for (int s = 0; s < d->n_scales; ++s) p.dsrc = p.dsrc || d->d_src[s] != nullptr;
-  p.wide = grad && !p.dsrc && !p.ref && !p.ssim && !p.expl && !tuning().no_wide && max_items(d, sw) <= (long long)cus * 4 * 3;
-  // Two sources per pass (loss_kernel_pair): the SSIM gradient launches of the pixel-interleaved layout with an even number of
-  // sources, without the warped output.  By default where it measured faster (profiles/r06_pair_kernel.txt): launches whose
-  // one-source plan has to cut the largest scale into chunks of at most PAIR_BELOW_ROWS rows to fill the chip (B <= 24 at 128x416:
-  // -2 ... -12 % kernel time; the halo rows of short chunks are what the taller chunks of two thirds as many waves save).  At
-  // BASELINE cfg3 / cfg5 (15 / 13 rows) it is 1 - 5 % SLOWER -- 11 % fewer vector instructions, issued 12 % less densely by two
-  // waves per SIMD than by three -- and is not used.
-  p.pair = false;
-  if (grad && p.ssim && p.hwc && !p.dsrc && !p.ref && !p.warped && d->n_src % 2 == 0) {
-    int rows1[SFM_MAX_SCALES];
-    plan_chunks(d, sw, 2 * (hs > hm ? hs : hm), cus * 4 * 3, d->n_src, rows1);
-    p.pair = rows1[0] <= PAIR_BELOW_ROWS;
-    if (tuning().pair >= 0) p.pair = tuning().pair != 0;
-    if (pair_hook >= 0) p.pair = pair_hook != 0;
-  }
-  const int waves_per_simd = waves_per_simd_of(p.ssim, grad, p.wide, p.dsrc, p.pair);
-  const int slots = cus * 4 * waves_per_simd;
-  A.simds_per_xcd = (cus % 8 == 0) ? cus / 8 * 4 : 128;   // gfx950: 8 XCDs, 4 SIMDs per CU
-  A.prio_top = waves_per_simd - 1 < 3 ? waves_per_simd - 1 : 3;
-  A.prio_tab = 0;
-  for (int r = 0; r <= A.prio_top; ++r)   // youngest preferred in the first half of the sources, oldest in the second
-    A.prio_tab |= (unsigned)r << (2 * r) | (unsigned)(A.prio_top - r) << (8 + 2 * r);
-  if (tuning().has_prio) A.prio_tab = tuning().prio_tab & 0xffffu;
-  if (d->B < (tuning().deal_below > 8 ? tuning().deal_below : 8)) A.prio_tab |= 0x80000000u;   // fewer samples than XCDs (or asked for): deal items
-  plan_chunks(d, sw, 2 * (hs > hm ? hs : hm), slots, p.pair ? d->n_src / 2 : d->n_src, rows);
-  int items = 0;
   for (int s = 0; s < d->n_scales; ++s) {
     const int h = d->H[s], w = d->W[s];
     if (h < 3 || w < 3) return fail(SFM_ERR_SHAPE, "sfm_loss: scale %d is %dx%d, need H,W >= 3", s, h, w);
     if ((long long)d->B * 3 * d->n_src * h * w >= (1ll << 31)) return fail(SFM_ERR_SHAPE, "sfm_loss: scale %d too large", s);
     // (byte offsets inside one pixel-interleaved image are formed exactly in fp32 by the gather of the HWC kernels)
-    if (p.hwc && (long long)h * w * 12 >= (1ll << 24))
+    if (d->image_layout == SFM_LAYOUT_HWC && (long long)h * w * 12 >= (1ll << 24))
       return fail(SFM_ERR_SHAPE, "sfm_loss: scale %d is %dx%d, SFM_LAYOUT_HWC takes images of fewer than 2^24 / 12 pixels", s, h, w);
     if (!d->tgt[s] || !d->src[s] || !d->disp[s]) return fail(SFM_ERR_NULL, "sfm_loss: tgt/src/disp[%d] is NULL", s);
     // (the second launch of a call with d_src addresses the record of one (sample, source) with 32-bit byte offsets)
     if (d->d_src[s] && (long long)h * w * 12 >= (1ll << 32)) return fail(SFM_ERR_SHAPE, "sfm_loss: scale %d is %dx%d, d_src takes images of fewer than 2^32 / 12 pixels", s, h, w);
-    if (p.expl && !d->mask_logits[s]) return fail(SFM_ERR_NULL, "sfm_loss: exp_reg > 0 but mask_logits[%d] is NULL", s);
+    if (d->exp_reg > 0.f && !d->mask_logits[s]) return fail(SFM_ERR_NULL, "sfm_loss: exp_reg > 0 but mask_logits[%d] is NULL", s);
+  }
+  return SFM_OK;
+}
+
+// the arrays the entry point writes (a valid descriptor)
+static int validate_outputs(const SfmLossDesc* d, const Entry e) {
+  if (e.loss) {      // the optional warped-image output: an array for every scale or for none
+    int n_w = 0;
+    for (int s = 0; s < d->n_scales; ++s) n_w += d->warped[s] != nullptr;
+    if (n_w != 0 && n_w != d->n_scales) return fail(SFM_ERR_NULL, "sfm_loss: warped[] is set for %d of %d scales (all or none)", n_w, d->n_scales);
+  }
+  if (!e.grad) return SFM_OK;
+  for (int i = 0; i < d->n_src; ++i)
+    if (!d->d_pose[i]) return fail(SFM_ERR_NULL, "sfm_loss: d_pose[%d] is NULL", i);
+  for (int s = 0; s < d->n_scales; ++s) {
+    if (!d->d_disp[s]) return fail(SFM_ERR_NULL, "sfm_loss: d_disp[%d] is NULL", s);
+    if (d->exp_reg > 0.f && !d->d_mask[s]) return fail(SFM_ERR_NULL, "sfm_loss: exp_reg > 0 but d_mask[%d] is NULL", s);
+  }
+  return SFM_OK;
+}
+
+static bool any_bound(float* const* arr, const int n) {
+  for (int s = 0; s < n; ++s)
+    if (arr[s]) return true;
+  return false;
+}
+
+// Which kernel serves the launch.  It follows from the descriptor's pointers whether or not the call checks its outputs, so that
+// sfm_loss_plan_info reports the launch the call will make.  `pair_hook`: 0 / 1 = the one-call hook's choice, -1 = none.
+static Variant choose_variant(const SfmLossDesc* d, const Entry e, const int cus, const int pair_hook) {
+  Variant v = {};
+  v.grad = e.grad;
+  v.loss = e.loss;
+  v.expl = d->exp_reg > 0.f;                       // base_model.py:86,103
+  v.ssim = !v.expl && d->ssim_rate > 0.f;          // base_model.py:110-112
+  v.smode = d->smooth_reg > 0.f ? d->smooth_mode : SFM_SMOOTH_NONE;   // base_model.py:75
+  v.hwc = d->image_layout == SFM_LAYOUT_HWC;
+  v.warped = e.loss && any_bound(d->warped, d->n_scales);
+  v.family = Family::Base;
+  const HaloCols hc = halo_of(v);
+  if (d->projection == SFM_PROJECTION_REFERENCE_ORDER) {
+    v.family = Family::Ref;                        // (these kernels record dL/dI^ themselves when d_src is bound)
+  } else if (e.grad && any_bound(d->d_src, d->n_scales)) {
+    v.family = Family::Dsrc;
+  } else if (e.grad && v.ssim && v.hwc && !v.warped && d->n_src % 2 == 0) {
+    // Two sources per pass (loss_kernel_pair): the SSIM gradient launches of the pixel-interleaved layout with an even number of
+    // sources, without the warped output.  By default where it measured faster (profiles/r06_pair_kernel.txt): launches whose
+    // one-source plan has to cut the largest scale into chunks of at most PAIR_BELOW_ROWS rows to fill the chip (B <= 24 at 128x416:
+    // -2 ... -12 % kernel time; the halo rows of short chunks are what the taller chunks of two thirds as many waves save).  At
+    // BASELINE cfg3 / cfg5 (15 / 13 rows) it is 1 - 5 % SLOWER -- 11 % fewer vector instructions, issued 12 % less densely by two
+    // waves per SIMD than by three -- and is not used.
+    int rows1[SFM_MAX_SCALES];
+    plan_chunks(d, hc.sw, 2 * hc.hr, cus * 4 * waves_per_simd(v), d->n_src, rows1);
+    bool pair = rows1[0] <= PAIR_BELOW_ROWS;
+    if (tuning().pair >= 0) pair = tuning().pair != 0;
+    if (pair_hook >= 0) pair = pair_hook != 0;
+    if (pair) v.family = Family::Pair;
+  } else if (e.grad && !v.ssim && !v.expl && !tuning().no_wide &&
+             max_items(d, hc.sw) <= (long long)cus * 4 * waves_per_simd(Family::Wide, false, true)) {
+    v.family = Family::Wide;   // (a launch is "small" when even at the smallest chunk height its waves fit the SIMDs three deep)
+  }
+  return v;
+}
+
+static const void* kernel_of(const Variant& v) {
+  switch (v.family) {
+    case Family::Wide: return lift_variant<Family::Wide>(v);
+    case Family::Pair: return kernel_of_pair(v);
+    case Family::Ref: return kernel_of_ref(v);
+    case Family::Dsrc: return kernel_of_dsrc(v);
+    default: return lift_variant<Family::Base>(v);
+  }
+}
+
+// the inputs, the outputs of the entry point (validate_outputs has seen them where the plan is one a call launches) and the
+// per-scale constants
+static void fill_args(const SfmLossDesc* d, const Variant& v, LossArgs& A) {
+  memset(&A, 0, sizeof(A));
+  A.B = d->B;
+  A.n_src = d->n_src;
+  A.n_scales = d->n_scales;
+  A.alpha = d->ssim_rate;
+  A.intrinsics = d->intrinsics;
+  for (int i = 0; i < d->n_src; ++i) {
+    A.pose[i] = d->pose[i];
+    if (v.grad) A.d_pose[i] = d->d_pose[i];
+  }
+  for (int s = 0; s < d->n_scales; ++s) {
     ScaleArgs& S = A.sc[s];
+    const int h = d->H[s], w = d->W[s];
     S.tgt = d->tgt[s];
     S.src = d->src[s];
     S.disp = d->disp[s];
-    S.mlog = p.expl ? d->mask_logits[s] : nullptr;
-    S.warped = (need_loss && need_outputs) ? d->warped[s] : nullptr;
-    if (grad && need_outputs) {
-      if (!d->d_disp[s]) return fail(SFM_ERR_NULL, "sfm_loss: d_disp[%d] is NULL", s);
-      if (p.expl && !d->d_mask[s]) return fail(SFM_ERR_NULL, "sfm_loss: exp_reg > 0 but d_mask[%d] is NULL", s);
+    S.mlog = v.expl ? d->mask_logits[s] : nullptr;
+    S.warped = v.loss ? d->warped[s] : nullptr;
+    if (v.grad) {
       S.d_disp = d->d_disp[s];
-      S.d_mask = p.expl ? d->d_mask[s] : nullptr;
+      S.d_mask = v.expl ? d->d_mask[s] : nullptr;
       S.d_src = d->d_src[s];
     }
     S.h = h;
     S.w = w;
-    S.strips = (w + sw - 1) / sw;
-    S.chunk_rows = rows[s];
-    S.chunks = (h + rows[s] - 1) / rows[s];
-    S.tiles = S.strips * S.chunks;
-    S.item_begin = items;
-    A.tiles_of[s] = S.tiles;
-    A.item_begin_of[s] = items;
-    items += d->B * S.tiles;
     const double nb = (double)d->norm_B;
     S.inv_cnt = (float)(1.0 / (nb * 3.0 * h * w));
     const double wgt = (double)d->smooth_reg / (double)(1 << s);               // base_model.py:76
@@ -621,18 +634,78 @@ static int make_plan(const SfmLossDesc* d, bool grad, bool need_loss, bool need_
     S.c_ey = (float)(wgt / (nb * (h - 1) * w));
     S.c_exp = (float)((double)d->exp_reg / (nb * h * w));
   }
+}
+
+// the items of the launch: chunk heights, tiles per scale, and how the waves of a SIMD share it (issue priorities, dealing)
+static void plan_items(const SfmLossDesc* d, const Variant& v, const int cus, LossArgs& A) {
+  const HaloCols hc = halo_of(v);
+  const int waves = waves_per_simd(v);
+  A.simds_per_xcd = (cus % 8 == 0) ? cus / 8 * 4 : 128;   // gfx950: 8 XCDs, 4 SIMDs per CU
+  A.prio_top = waves - 1 < 3 ? waves - 1 : 3;
+  A.prio_tab = 0;
+  for (int r = 0; r <= A.prio_top; ++r)   // youngest preferred in the first half of the sources, oldest in the second
+    A.prio_tab |= (unsigned)r << (2 * r) | (unsigned)(A.prio_top - r) << (8 + 2 * r);
+  if (tuning().has_prio) A.prio_tab = tuning().prio_tab & 0xffffu;
+  if (d->B < (tuning().deal_below > 8 ? tuning().deal_below : 8)) A.prio_tab |= 0x80000000u;   // fewer samples than XCDs (or asked for): deal items
+  int rows[SFM_MAX_SCALES];
+  plan_chunks(d, hc.sw, 2 * hc.hr, cus * 4 * waves, d->n_src / sources_per_pass(v.family), rows);
+  int items = 0;
+  for (int s = 0; s < d->n_scales; ++s) {
+    ScaleArgs& S = A.sc[s];
+    S.strips = (S.w + hc.sw - 1) / hc.sw;
+    S.chunk_rows = rows[s];
+    S.chunks = (S.h + rows[s] - 1) / rows[s];
+    S.tiles = S.strips * S.chunks;
+    S.item_begin = items;
+    A.tiles_of[s] = S.tiles;
+    A.item_begin_of[s] = items;
+    items += d->B * S.tiles;
+  }
   A.items = items;
-  set_gy(p, gy);
-  // The workspace layout does not depend on the chunking (nor on the device): the two partial-sum arrays are placed
-  // and sized for the largest item count any chunking can produce.
-  const size_t cap = (size_t)max_items(d, sw);
-  if ((size_t)items > cap) return fail(SFM_ERR_CONFIG, "sfm_loss: internal error: %d items exceed the bound %zu", items, cap);
+}
+
+// The preloaded header: B, n_src, n_scales and the tile counts packed, where they fit their fields.
+static PackedHdr pack_header(const LossArgs& A) {
+  PackedHdr h = {};
+  h.compact = A.B <= (int)HDR_B_MASK && A.n_src <= (int)HDR_NIBBLE && A.n_scales <= (int)HDR_NIBBLE;
+  for (int k = 0; k < SFM_MAX_SCALES; ++k) h.compact = h.compact && A.tiles_of[k] >= 0 && A.tiles_of[k] <= (int)HDR_TILE_MASK;
+  if (!h.compact) return h;
+  h.bsc = (unsigned)A.B | (unsigned)A.n_src << HDR_SRC_SHIFT | (unsigned)A.n_scales << HDR_SCALES_SHIFT;
+  for (int k = 0; k < SFM_MAX_SCALES; ++k) h.tiles[hdr_tile_word(k)] |= (unsigned)A.tiles_of[k] << hdr_tile_shift(k);
+  return h;
+}
+
+static void set_gy(Plan& p, const float gy);
+static void plan_dsrc(const SfmLossDesc* d, const int cus, Plan& p);
+
+// The workspace layout does not depend on the chunking (nor on the device): the two partial-sum arrays are placed
+// and sized for the largest item count any chunking can produce.
+static int plan_workspace(const SfmLossDesc* d, const int cus, Plan& p) {
+  const size_t cap = (size_t)max_items(d, halo_of(p.v).sw);
+  if ((size_t)p.args.items > cap) return fail(SFM_ERR_CONFIG, "sfm_loss: internal error: %d items exceed the bound %zu", p.args.items, cap);
   p.off_loss = 0;
   p.off_gpm = align_up(p.off_loss + cap * 4 * sizeof(float), 256);
   p.total = align_up(p.off_gpm + cap * d->n_src * 12 * sizeof(float), 256);
   // dL/d(src): the record of dL/dI^ per scale that binds d_src (whatever the entry point: the workspace is sized from the descriptor)
   plan_dsrc(d, cus, p);
   return SFM_OK;
+}
+
+// validates the descriptor and lays out items + workspace for the given entry point
+static int make_plan(const SfmLossDesc* d, const Entry e, const Outputs out, const float gy, Plan& p, const int pair_hook = -1) {
+  if (int err = validate(d)) return err;
+  if (out == Outputs::Checked)
+    if (int err = validate_outputs(d, e)) return err;
+  const int cus = device_cus();
+  p.v = choose_variant(d, e, cus, pair_hook);
+  p.dsrc = e.grad && any_bound(d->d_src, d->n_scales);
+  p.kernel = kernel_of(p.v);
+  if (!p.kernel) return fail(SFM_ERR_CONFIG, "sfm_loss: internal error: no kernel of family %d for this launch", (int)p.v.family);
+  fill_args(d, p.v, p.args);
+  plan_items(d, p.v, cus, p.args);
+  set_gy(p, gy);
+  p.hdr = pack_header(p.args);
+  return plan_workspace(d, cus, p);
 }
 
 // The second launch of a call with d_src bound: bands, window and workgroups (DsrcArgs), and the place of the records in the workspace.
@@ -709,68 +782,34 @@ static void bind_workspace(Plan& p, void* ws) {
       }
 }
 
-template <bool GRAD, bool LOSS>
-static const void* kernel_ptr(bool ssim, bool expl, int smode, bool hwc, bool wide, bool warped) {
-  // (WARPED only exists for the LOSS entry points: W = LOSS && warped is a constant false elsewhere, and those variants are not built)
-#define SFM_KPICK(NAME, ...)                                                                                              \
-  do {                                                                                                                    \
-    if constexpr (LOSS) {                                                                                                 \
-      if (warped) return hwc ? (const void*)&NAME<__VA_ARGS__, true, true> : (const void*)&NAME<__VA_ARGS__, false, true>; \
-    }                                                                                                                     \
-    return hwc ? (const void*)&NAME<__VA_ARGS__, true, false> : (const void*)&NAME<__VA_ARGS__, false, false>;            \
-  } while (0)
-  if (GRAD && wide && !ssim && !expl) {
-    if (smode == 0) SFM_KPICK(loss_kernel_wide, LOSS, 0);
-    else if (smode == 1) SFM_KPICK(loss_kernel_wide, LOSS, 1);
-    else SFM_KPICK(loss_kernel_wide, LOSS, 2);
-  }
-  if (expl) {
-    if (smode == 0) SFM_KPICK(loss_kernel, false, GRAD, LOSS, true, 0);
-    else if (smode == 1) SFM_KPICK(loss_kernel, false, GRAD, LOSS, true, 1);
-    else SFM_KPICK(loss_kernel, false, GRAD, LOSS, true, 2);
-  } else if (ssim) {
-    if (smode == 0) SFM_KPICK(loss_kernel, true, GRAD, LOSS, false, 0);
-    else if (smode == 1) SFM_KPICK(loss_kernel, true, GRAD, LOSS, false, 1);
-    else SFM_KPICK(loss_kernel, true, GRAD, LOSS, false, 2);
-  } else {
-    if (smode == 0) SFM_KPICK(loss_kernel, false, GRAD, LOSS, false, 0);
-    else if (smode == 1) SFM_KPICK(loss_kernel, false, GRAD, LOSS, false, 1);
-    else SFM_KPICK(loss_kernel, false, GRAD, LOSS, false, 2);
-  }
-#undef SFM_KPICK
-}
-
-template <bool GRAD, bool LOSS>
-static hipError_t launch_main(const Plan& p, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, const int variant) {
+static hipError_t launch_main(const Plan& p, const Hooks& hooks, hipStream_t st) {
   LossArgs args = p.args;
-  // the preloaded header (make_hdr): B, n_src, n_scales, prio_top and the tile counts packed
-  // (sfm_loss_variant(3), tests: the header read from the struct, the path of counts beyond 16 bits)
-  bool compact = variant != 3 && args.B <= 0xffff && args.n_src <= 15 && args.n_scales <= 15 && args.prio_top <= 3;
-  for (int k = 0; k < SFM_MAX_SCALES; ++k) compact = compact && args.tiles_of[k] >= 0 && args.tiles_of[k] <= 0xffff;
-  unsigned h_bn = 0, h_t[4] = {0, 0, 0, 0}, h_prio = args.prio_tab;
-  int h_items = args.items, h_simds = args.simds_per_xcd;
-  unsigned long long* h_trace = args.trace;
-  if (compact) {
-    h_bn = (unsigned)args.B | (unsigned)args.n_src << 16 | (unsigned)args.n_scales << 20 | (unsigned)args.prio_top << 24 | 1u << 31;
-    for (int k = 0; k < SFM_MAX_SCALES; ++k) h_t[k >> 1] |= (unsigned)args.tiles_of[k] << (16 * (k & 1));
-  }
-  void* kargs[] = {&h_bn, &h_items, &h_simds, &h_prio, &h_t[0], &h_t[1], &h_t[2], &h_t[3], &h_trace, &args};
+  // the preloaded header (make_hdr); HOOK_STRUCT_HEADER (tests): the header read from the struct
+  const PackedHdr hdr = hooks.variant == HOOK_STRUCT_HEADER ? PackedHdr{} : p.hdr;
+  unsigned h_bn = hdr.compact ? hdr.bsc | (unsigned)args.prio_top << HDR_PRIO_SHIFT | 1u << HDR_COMPACT_BIT : 0u;
+  unsigned h_t[4] = {hdr.tiles[0], hdr.tiles[1], hdr.tiles[2], hdr.tiles[3]};
+  void* kargs[] = {&h_bn, &args.items, &args.simds_per_xcd, &args.prio_tab, &h_t[0], &h_t[1], &h_t[2], &h_t[3], &args.trace, &args};
   // 8 x (items of the busiest XCD): see the item mapping at the top of loss_kernel
   int tiles_per_sample = 0;
   for (int s = 0; s < p.args.n_scales; ++s) tiles_per_sample += p.args.sc[s].tiles;
   const int per_xcd = (int)p.args.prio_tab >= 0 ? (p.args.B / 8) * tiles_per_sample + ((p.args.B % 8) * tiles_per_sample + 7) / 8 : (p.args.items + 7) / 8;
-  const void* fn = kernel_ptr<GRAD, LOSS>(p.ssim, p.expl, p.smode, p.hwc, p.wide, p.warped);
-  if (p.ref) fn = kernel_ptr_ref(GRAD, LOSS, p.ssim, p.expl, p.smode, p.hwc, p.warped);      // SFM_PROJECTION_REFERENCE_ORDER
-  if (p.pair) fn = kernel_ptr_pair(GRAD, LOSS, p.smode);                                     // two sources per pass
-  if constexpr (GRAD) {
-    if (p.dsrc && !p.ref) fn = kernel_ptr_dsrc(LOSS, p.ssim, p.expl, p.smode, p.hwc, p.warped);      // (the REF kernels record dL/dI^ themselves)
-  }
   // With profiling events the kernel is launched through hipExtLaunchKernel: the events then carry the begin / end
   // timestamps of THIS dispatch (what rocprofv3's kernel trace reports), and no marker packets are put between the
   // launches of a step (hipEventRecord on either side of the kernel costs the step several microseconds).
   const size_t smem = 0;
-  if (ev_start && ev_stop) return hipExtLaunchKernel(fn, dim3(8 * per_xcd), dim3(64 * WAVES_PER_BLOCK), kargs, smem, st, ev_start, ev_stop, 0);
-  return hipLaunchKernel(fn, dim3(8 * per_xcd), dim3(64 * WAVES_PER_BLOCK), kargs, smem, st);
+  if (hooks.ev_start && hooks.ev_stop)
+    return hipExtLaunchKernel(p.kernel, dim3(8 * per_xcd), dim3(64 * WAVES_PER_BLOCK), kargs, smem, st, hooks.ev_start, hooks.ev_stop, 0);
+  return hipLaunchKernel(p.kernel, dim3(8 * per_xcd), dim3(64 * WAVES_PER_BLOCK), kargs, smem, st);
+}
+
+static void launch_finalize(const Plan& p, const Hooks& hooks, float* loss5, hipStream_t st) {
+  const LossArgs& a = p.args;
+  const PackedHdr hdr = hooks.variant == HOOK_STRUCT_HEADER ? PackedHdr{} : p.hdr;
+  const unsigned bsc = (hdr.compact ? hdr.bsc | FIN_COMPACT : 0u) | (p.v.grad ? FIN_POSE : 0u) | (p.v.loss ? FIN_LOSS : 0u);
+  const int n_pose_blocks = p.v.grad ? a.B * a.n_src : 0;
+  hipLaunchKernelGGL(finalize_kernel, dim3(n_pose_blocks + 1), dim3(64 * FINALIZE_WAVES), 0, st, (const float*)a.part_gpm, a.intrinsics, a.pose[0],
+                     a.pose[1], bsc, hdr.tiles[0], hdr.tiles[1], hdr.tiles[2], hdr.tiles[3], (unsigned)(p.off_gpm - p.off_loss), a,
+                     p.v.loss ? loss5 : (float*)nullptr);
 }
 
 // The plan of a descriptor depends only on the descriptor's bytes and the entry point: the last few are kept per
@@ -779,87 +818,73 @@ static hipError_t launch_main(const Plan& p, hipStream_t st, hipEvent_t ev_start
 struct CachedPlan {
   SfmLossDesc desc;
   int device, pair_hook;
-  bool grad, loss, valid;
+  Entry entry;
+  bool valid;
   Plan plan;
 };
 constexpr int PLAN_CACHE = 4;
 static thread_local CachedPlan g_plans[PLAN_CACHE];
 static thread_local unsigned g_plan_clock = 0;
 
-static int cached_plan(const SfmLossDesc* d, bool grad, bool loss, float gy, Plan& out, const int pair_hook) {
+static int cached_plan(const SfmLossDesc* d, const Entry e, float gy, Plan& out, const int pair_hook) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
   for (int k = 0; k < PLAN_CACHE; ++k) {
     CachedPlan& c = g_plans[k];
-    if (c.valid && c.grad == grad && c.loss == loss && c.device == dev && c.pair_hook == pair_hook && memcmp(&c.desc, d, sizeof(SfmLossDesc)) == 0) {
+    if (c.valid && c.entry.grad == e.grad && c.entry.loss == e.loss && c.device == dev && c.pair_hook == pair_hook &&
+        memcmp(&c.desc, d, sizeof(SfmLossDesc)) == 0) {
       out = c.plan;
       set_gy(out, gy);
       return SFM_OK;
     }
   }
-  if (int e = make_plan(d, grad, loss, true, gy, out, pair_hook)) return e;
+  if (int err = make_plan(d, e, Outputs::Checked, gy, out, pair_hook)) return err;
   CachedPlan& c = g_plans[g_plan_clock++ % PLAN_CACHE];
-  c.desc = *d; c.device = dev; c.pair_hook = pair_hook; c.grad = grad; c.loss = loss; c.plan = out; c.valid = true;
+  c.desc = *d; c.device = dev; c.pair_hook = pair_hook; c.entry = e; c.plan = out; c.valid = true;
   return SFM_OK;
 }
 
-// `tgt_full` / `src_full` (sfm_step_*): the full-resolution frames whose pyramids are written into d->tgt[] / d->src[] first -- after
-// every argument of the call has been checked, so that a rejected call has launched nothing and written nothing.
-static int run(const SfmLossDesc* d, bool grad, bool loss, float gy, float* loss5, void* ws, size_t ws_bytes, void* stream,
-               const char* who, const float* tgt_full = nullptr, const float* src_full = nullptr, bool from_frames = false) {
+// `frames` (sfm_step_*): the full-resolution frames whose pyramids are written into d->tgt[] / d->src[] first -- after every
+// argument of the call has been checked, so that a rejected call has launched nothing and written nothing.  nullptr: sfm_loss_*.
+struct Frames { const float *tgt, *src; };
+
+static int run(const SfmLossDesc* d, const Entry e, float gy, float* loss5, void* ws, size_t ws_bytes, void* stream, const char* who,
+               const Frames* frames) {
   hipStream_t st = (hipStream_t)stream;
   // the one-call hooks are taken -- and forgotten -- here, whatever becomes of the call
-  const int variant = g_variant;
-  g_variant = 0;
-  unsigned long long* const trace = g_trace;
-  g_trace = nullptr;
-  hipEvent_t ev_start = g_ev_start, ev_stop = g_ev_stop;
-  g_ev_start = g_ev_stop = nullptr;
+  const Hooks hooks = g_hooks;
+  g_hooks = Hooks{};
   if (d && d->B == 0) {   // empty shard: nothing to launch (input pointers of empty arrays may be NULL)
-    if (loss) {
+    if (e.loss) {
       if (!loss5) return fail(SFM_ERR_NULL, "%s: loss5 is NULL", who);
-      hipError_t e = hipMemsetAsync(loss5, 0, 5 * sizeof(float), st);
-      if (e != hipSuccess) return fail((int)e, "%s: memset: %s", who, hipGetErrorString(e));
+      hipError_t err = hipMemsetAsync(loss5, 0, 5 * sizeof(float), st);
+      if (err != hipSuccess) return fail((int)err, "%s: memset: %s", who, hipGetErrorString(err));
     }
     return SFM_OK;
   }
   if (!d) return fail(SFM_ERR_NULL, "%s: NULL descriptor", who);
   Plan p;
-  // (sfm_loss_variant 4 / 5: one source per pass / two sources per pass where possible, whatever the default -- in-process A/B, tests)
-  if (int e = cached_plan(d, grad, loss, gy, p, variant == 4 ? 0 : (variant == 5 ? 1 : -1))) return e;
-  if (loss && !loss5) return fail(SFM_ERR_NULL, "%s: loss5 is NULL", who);
+  if (int err = cached_plan(d, e, gy, p, pair_hook_of(hooks.variant))) return err;
+  if (e.loss && !loss5) return fail(SFM_ERR_NULL, "%s: loss5 is NULL", who);
   if (!ws || ws_bytes < p.total) return fail(SFM_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, got %zu", who, p.total, ws_bytes);
   if (((uintptr_t)ws & 255) != 0) return fail(SFM_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
-  if (from_frames)
-    if (int e = sfm_pyramid_pair_hwc_fwd(tgt_full, src_full, (float* const*)d->tgt, (float* const*)d->src, d->B, d->n_src, d->H[0], d->W[0],
-                                         d->n_scales, stream))
-      return e;
+  if (frames)
+    if (int err = sfm_pyramid_pair_hwc_fwd(frames->tgt, frames->src, (float* const*)d->tgt, (float* const*)d->src, d->B, d->n_src, d->H[0],
+                                           d->W[0], d->n_scales, stream))
+      return err;
   bind_workspace(p, ws);
-  p.args.trace = trace;
-  hipError_t le;
-  if (grad && loss) le = launch_main<true, true>(p, st, ev_start, ev_stop, variant);
-  else if (grad) le = launch_main<true, false>(p, st, ev_start, ev_stop, variant);
-  else le = launch_main<false, true>(p, st, ev_start, ev_stop, variant);
+  p.args.trace = hooks.trace;
+  hipError_t le = launch_main(p, hooks, st);
   if (le != hipSuccess) return fail((int)le, "%s: launch of the main kernel: %s", who, hipGetErrorString(le));
-  if (grad && p.dsrc) {      // dL/d(src) from the record the main launch has just written
+  if (p.dsrc) {      // dL/d(src) from the record the main launch has just written
     le = launch_dsrc_scatter(p.dsrc_args, st);
     if (le != hipSuccess) return fail((int)le, "%s: launch of the d_src kernel: %s", who, hipGetErrorString(le));
   }
-  const int n_pose_blocks = grad ? d->B * d->n_src : 0;
-  {
-    const LossArgs& a = p.args;
-    bool compact = variant != 3 && a.B <= 0xffff && a.n_src <= 15 && a.n_scales <= 15;
-    for (int k = 0; k < SFM_MAX_SCALES; ++k) compact = compact && a.tiles_of[k] >= 0 && a.tiles_of[k] <= 0xffff;
-    unsigned tw[4] = {0, 0, 0, 0};
-    if (compact)
-      for (int k = 0; k < SFM_MAX_SCALES; ++k) tw[k >> 1] |= (unsigned)a.tiles_of[k] << (16 * (k & 1));
-    const unsigned bsc = (compact ? ((unsigned)a.B | (unsigned)a.n_src << 16 | (unsigned)a.n_scales << 20 | FIN_COMPACT) : 0u) |
-                         (grad ? FIN_POSE : 0u) | (loss ? FIN_LOSS : 0u);
-    hipLaunchKernelGGL(finalize_kernel, dim3(n_pose_blocks + 1), dim3(64 * FINALIZE_WAVES), 0, st, (const float*)a.part_gpm, a.intrinsics,
-                       a.pose[0], a.pose[1], bsc, tw[0], tw[1], tw[2], tw[3], (unsigned)(p.off_gpm - p.off_loss), p.args, loss ? loss5 : (float*)nullptr);
-  }
+  launch_finalize(p, hooks, loss5, st);
   return check_launch(who);
 }
+
+constexpr Entry ENTRY_FWD = {false, true}, ENTRY_BWD = {true, false}, ENTRY_FWD_BWD = {true, true};
 
 }  // namespace sfm
 
@@ -868,10 +893,9 @@ extern "C" {
 size_t sfm_loss_workspace_bytes(const SfmLossDesc* desc) {
   // the three entry points lay their work out differently: size for the largest
   size_t total = 0;
-  const bool modes[3][2] = {{false, true}, {true, false}, {true, true}};
-  for (int m = 0; m < 3; ++m) {
+  for (const sfm::Entry e : {sfm::ENTRY_FWD, sfm::ENTRY_BWD, sfm::ENTRY_FWD_BWD}) {
     sfm::Plan p;
-    if (sfm::make_plan(desc, modes[m][0], modes[m][1], false, 1.f, p) != SFM_OK) return 0;
+    if (sfm::make_plan(desc, e, sfm::Outputs::Unchecked, 1.f, p) != SFM_OK) return 0;
     if (p.total > total) total = p.total;
   }
   return total;
@@ -879,7 +903,7 @@ size_t sfm_loss_workspace_bytes(const SfmLossDesc* desc) {
 
 int sfm_loss_plan_info(const SfmLossDesc* desc, int grad, int loss, int* out, int n_out) {
   sfm::Plan p;
-  if (int e = sfm::make_plan(desc, grad != 0, loss != 0, false, 1.f, p)) return e;
+  if (int e = sfm::make_plan(desc, sfm::Entry{grad != 0, loss != 0}, sfm::Outputs::Unchecked, 1.f, p)) return e;
   if (!out || n_out < 1 + 4 * desc->n_scales) return sfm::fail(SFM_ERR_NULL, "sfm_loss_plan_info: out needs 1 + 4 * n_scales ints");
   out[0] = p.args.items;
   for (int s = 0; s < desc->n_scales; ++s) {
@@ -887,36 +911,41 @@ int sfm_loss_plan_info(const SfmLossDesc* desc, int grad, int loss, int* out, in
     int* o = out + 1 + 4 * s;
     o[0] = S.strips; o[1] = S.chunks; o[2] = S.chunk_rows; o[3] = S.tiles;
   }
+  if (n_out >= 1 + 4 * desc->n_scales + 2) {      // the kernel family of the main launch and its resident waves per SIMD
+    out[1 + 4 * desc->n_scales] = (int)p.v.family;
+    out[2 + 4 * desc->n_scales] = sfm::waves_per_simd(p.v);
+  }
   return SFM_OK;
 }
 
 int sfm_loss_variant(int variant) {
-  if (variant != 0 && (variant < 3 || variant > 5)) return sfm::fail(SFM_ERR_CONFIG, "sfm_loss_variant: %d is not 0, 3, 4 or 5", variant);
-  sfm::g_variant = variant;
+  if (variant != 0 && (variant < sfm::HOOK_STRUCT_HEADER || variant > sfm::HOOK_TWO_SOURCES))
+    return sfm::fail(SFM_ERR_CONFIG, "sfm_loss_variant: %d is not 0, 3, 4 or 5", variant);
+  sfm::g_hooks.variant = variant;
   return SFM_OK;
 }
 
 int sfm_loss_debug_trace(void* buf) {
-  sfm::g_trace = (unsigned long long*)buf;
+  sfm::g_hooks.trace = (unsigned long long*)buf;
   return SFM_OK;
 }
 
 int sfm_loss_profile_events(void* ev_start, void* ev_stop) {
-  sfm::g_ev_start = (hipEvent_t)ev_start;
-  sfm::g_ev_stop = (hipEvent_t)ev_stop;
+  sfm::g_hooks.ev_start = (hipEvent_t)ev_start;
+  sfm::g_hooks.ev_stop = (hipEvent_t)ev_stop;
   return SFM_OK;
 }
 
 int sfm_loss_fwd(const SfmLossDesc* desc, float* loss5, void* ws, size_t ws_bytes, void* stream) {
-  return sfm::run(desc, false, true, 1.f, loss5, ws, ws_bytes, stream, "sfm_loss_fwd");
+  return sfm::run(desc, sfm::ENTRY_FWD, 1.f, loss5, ws, ws_bytes, stream, "sfm_loss_fwd", nullptr);
 }
 
 int sfm_loss_bwd(const SfmLossDesc* desc, float gy, void* ws, size_t ws_bytes, void* stream) {
-  return sfm::run(desc, true, false, gy, nullptr, ws, ws_bytes, stream, "sfm_loss_bwd");
+  return sfm::run(desc, sfm::ENTRY_BWD, gy, nullptr, ws, ws_bytes, stream, "sfm_loss_bwd", nullptr);
 }
 
 int sfm_loss_fwd_bwd(const SfmLossDesc* desc, float* loss5, void* ws, size_t ws_bytes, void* stream) {
-  return sfm::run(desc, true, true, 1.f, loss5, ws, ws_bytes, stream, "sfm_loss_fwd_bwd");
+  return sfm::run(desc, sfm::ENTRY_FWD_BWD, 1.f, loss5, ws, ws_bytes, stream, "sfm_loss_fwd_bwd", nullptr);
 }
 
 // One step of SFMLearner.__call__ from the full-resolution frames (models/base_model.py:48-124) in ONE call: the loop head :69-72 --
@@ -933,7 +962,8 @@ static int step_from_frames(const float* tgt_full, const float* src_full, const 
                        d->W[s], d->H[0], d->W[0], d->H[0] >> s, d->W[0] >> s);
   // (the descriptor's pyramid pointers are inputs of the loss and outputs of this call: the caller owns the buffers either way.
   //  sfm::run writes the pyramids -- sfm_pyramid_pair_hwc_fwd -- once it has accepted the descriptor, loss5 and the workspace)
-  const int rc = sfm::run(d, grad, true, 1.f, loss5, ws, ws_bytes, stream, who, tgt_full, src_full, true);
+  const sfm::Frames frames = {tgt_full, src_full};
+  const int rc = sfm::run(d, grad ? sfm::ENTRY_FWD_BWD : sfm::ENTRY_FWD, 1.f, loss5, ws, ws_bytes, stream, who, &frames);
   if (rc < 0) sfm_pyramid_variant(0);      // a rejected step has consumed the one-call pyramid hook too, like a rejected pyramid call
   return rc;
 }

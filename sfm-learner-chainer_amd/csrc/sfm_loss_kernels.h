@@ -55,22 +55,45 @@ struct LossArgs {
   ScaleArgs sc[SFM_MAX_SCALES];
 };
 
-template <bool SSIM, bool GRAD, int SMODE>
-struct Halo {
-  static constexpr int HS = SSIM ? (GRAD ? 2 : 1) : 0;              // reach of the photometric pass
-  static constexpr int HM = SMODE == 1 ? 2 : (SMODE == 2 ? 1 : 0);  // reach of the smoothness stencil
-  static constexpr int HR = HS > HM ? HS : HM;                      // right halo lanes
-  static constexpr int HL = GRAD ? HR : HS;                         // left halo lanes (forward smoothness terms look right/down only)
-  static constexpr int SW = 64 - HL - HR;                           // output columns per strip
+// What identifies the main kernel of a launch.  choose_variant (sfm_loss.hip) decides it once per plan; everything that follows from
+// it -- halo and strip width, resident waves per SIMD, sources per pass, the __global__ that runs -- is a function of this record.
+enum class Family : int {   // (the numbers are what sfm_loss_plan_info reports)
+  Base = 0,   // loss_kernel
+  Wide = 1,   // loss_kernel_wide: the L1 gradient kernels built for three waves per SIMD, for small launches
+  Pair = 2,   // loss_kernel_pair: two sources per pass (sfm_ssim_pair.h)
+  Ref = 3,    // loss_kernel_ref: SfmLossDesc.projection = SFM_PROJECTION_REFERENCE_ORDER
+  Dsrc = 4,   // loss_kernel_dsrc: gradient launches that record dL/dI^ for the second launch of a call with d_src bound
+};
+struct Variant {
+  bool grad, loss;   // entry point
+  bool ssim, expl;   // loss mode (neither: L1)
+  int smode;         // smoothness form in effect (SFM_SMOOTH_NONE when smooth_reg = 0)
+  bool hwc, warped;  // pixel-interleaved images; the instantiation that also writes SfmLossDesc.warped
+  Family family;
 };
 
-static int strip_width(bool ssim, bool grad, int smode) {
-  const int hs = ssim ? (grad ? 2 : 1) : 0;
-  const int hm = smode == 1 ? 2 : (smode == 2 ? 1 : 0);
-  const int hr = hs > hm ? hs : hm;
-  const int hl = grad ? hr : hs;
-  return 64 - hl - hr;
+struct HaloCols { int hs, hm, hr, hl, sw; };
+constexpr HaloCols halo_of(const bool ssim, const bool grad, const int smode) {
+  const int hs = ssim ? (grad ? 2 : 1) : 0;              // reach of the photometric pass
+  const int hm = smode == 1 ? 2 : (smode == 2 ? 1 : 0);  // reach of the smoothness stencil
+  const int hr = hs > hm ? hs : hm;                      // right halo lanes
+  const int hl = grad ? hr : hs;                         // left halo lanes (forward smoothness terms look right/down only)
+  return {hs, hm, hr, hl, 64 - hl - hr};                 // sw: output columns per strip
 }
+constexpr HaloCols halo_of(const Variant& v) { return halo_of(v.ssim, v.grad, v.smode); }
+template <bool SSIM, bool GRAD, int SMODE>
+struct Halo {
+  static constexpr int HS = halo_of(SSIM, GRAD, SMODE).hs, HR = halo_of(SSIM, GRAD, SMODE).hr, HL = halo_of(SSIM, GRAD, SMODE).hl,
+                       SW = halo_of(SSIM, GRAD, SMODE).sw;
+};
+// resident waves per SIMD: the second argument of the kernel's __launch_bounds__ AND what the planner fills the chip by (3 for the
+// SSIM gradient kernels and the wide build, 2 for two sources per pass, 4 otherwise; the kernels that record dL/dI^ run at the
+// occupancy of the others)
+constexpr int waves_per_simd(const Family f, const bool ssim, const bool grad) {
+  return f == Family::Pair ? 2 : (f == Family::Wide || (ssim && grad)) ? 3 : 4;
+}
+constexpr int waves_per_simd(const Variant& v) { return waves_per_simd(v.family, v.ssim, v.grad); }
+constexpr int sources_per_pass(const Family f) { return f == Family::Pair ? 2 : 1; }
 
 // ------------------------------------------------------------------------------------------
 // smoothness passes (one per wave, before the sources)
@@ -241,7 +264,7 @@ __device__ __forceinline__ void set_issue_prio(const int p) {   // s_setprio tak
 // WIDE: the L1 gradient kernels compiled a second time for three waves per SIMD (168 registers instead of 128).  A small launch
 // (BASELINE cfg1 / cfg2: fewer waves than three rounds of SIMDs even at the smallest chunk height) is bound by how fast ONE wave
 // gets through its instructions, not by how many waves a SIMD holds: cfg2's kernel 14.3 -> 13.4 us.  At B = 32 the same build is
-// 8.7 % slower than the four-wave one (profiles/r03_ab_small_kernels.txt), so the plan picks per launch (Plan::wide).
+// 8.7 % slower than the four-wave one (profiles/r03_ab_small_kernels.txt), so the plan picks per launch (choose_variant).
 // WARPED: the instantiations that also write the warped source images (SfmLossDesc.warped; LOSS kernels only).
 // REF: the projection of the source passes in the reference's own evaluation order per pixel (SfmLossDesc.projection =
 // SFM_PROJECTION_REFERENCE_ORDER; sfm_ssim_pass.h, ref_position) -- a test hook of one kernel in round 5, every launch since round 6.
@@ -252,6 +275,13 @@ __device__ __forceinline__ void set_issue_prio(const int p) {   // s_setprio tak
 // scale's entry (rounds 3-5: header, then entry: two dependent round trips with the whole chip waiting at the start of a launch).
 //   h_bn: B | n_src << 16 | n_scales << 20 | prio_top << 24 | COMPACT << 31;  h_t01 .. h_t67: tiles_of[] as 16-bit halves.
 // COMPACT = 0 (a tile count or B beyond 16 bits): the header is read from the struct, as before.
+// The layout, shared by the host's packer (pack_header, sfm_loss.hip) and the two device decoders (make_hdr, finalize_kernel):
+constexpr unsigned HDR_B_MASK = 0xffffu, HDR_SRC_SHIFT = 16, HDR_SCALES_SHIFT = 20, HDR_NIBBLE = 0xfu;   // B | n_src | n_scales: both launches
+constexpr unsigned HDR_PRIO_SHIFT = 24, HDR_PRIO_MASK = 0x3u, HDR_COMPACT_BIT = 31;                       // the main kernels' h_bn
+constexpr unsigned FIN_COMPACT = 1u << 24, FIN_POSE = 1u << 25, FIN_LOSS = 1u << 26;                      // finalize_kernel's q_bsc
+constexpr unsigned HDR_TILE_MASK = 0xffffu;                                                               // a tile count: half a word
+constexpr int hdr_tile_word(const int k) { return k >> 1; }
+constexpr int hdr_tile_shift(const int k) { return 16 * (k & 1); }
 #define SFM_HDR_PARAMS const unsigned h_bn, const int h_items, const int h_simds, const unsigned h_prio, const unsigned h_t01, const unsigned h_t23, \
                        const unsigned h_t45, const unsigned h_t67, unsigned long long* const h_trace
 #define SFM_HDR_ARGS h_bn, h_items, h_simds, h_prio, h_t01, h_t23, h_t45, h_t67, h_trace
@@ -263,15 +293,16 @@ struct Hdr {
 };
 __device__ __forceinline__ Hdr make_hdr(const LossArgs& A, SFM_HDR_PARAMS) {
   Hdr H;
-  if (h_bn >> 31) {      // (uniform)
-    H.B = (int)(h_bn & 0xffffu); H.n_src = (int)((h_bn >> 16) & 0xfu); H.n_scales = (int)((h_bn >> 20) & 0xfu); H.prio_top = (int)((h_bn >> 24) & 0x3u);
+  if (h_bn >> HDR_COMPACT_BIT) {      // (uniform)
+    H.B = (int)(h_bn & HDR_B_MASK); H.n_src = (int)((h_bn >> HDR_SRC_SHIFT) & HDR_NIBBLE); H.n_scales = (int)((h_bn >> HDR_SCALES_SHIFT) & HDR_NIBBLE);
+    H.prio_top = (int)((h_bn >> HDR_PRIO_SHIFT) & HDR_PRIO_MASK);
     H.items = h_items; H.simds_per_xcd = h_simds; H.prio_tab = h_prio; H.trace = h_trace;
     const unsigned tw[4] = {h_t01, h_t23, h_t45, h_t67};
     int run = 0;
 #pragma unroll
     for (int k = 0; k < SFM_MAX_SCALES; ++k) {
-      H.tiles_of[k] = (int)((tw[k >> 1] >> (16 * (k & 1))) & 0xffffu);
-      H.item_begin_of[k] = run;          // make_plan: item_begin of a scale = B x the tiles of the scales before it
+      H.tiles_of[k] = (int)((tw[hdr_tile_word(k)] >> hdr_tile_shift(k)) & HDR_TILE_MASK);
+      H.item_begin_of[k] = run;          // plan_items: item_begin of a scale = B x the tiles of the scales before it
       run += H.B * H.tiles_of[k];
     }
   } else {
@@ -311,7 +342,7 @@ __device__ __forceinline__ void loss_body(const Hdr& H, const LossArgs& A) {
   // (the header H: preloaded kernel arguments, see make_hdr)
   const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
   int s = 0, b, t;
-  if ((int)H.prio_tab >= 0) {      // (bit 31 of prio_tab: deal the ITEMS out over the XCDs instead, see make_plan)
+  if ((int)H.prio_tab >= 0) {      // (bit 31 of prio_tab: deal the ITEMS out over the XCDs instead, see plan_items, sfm_loss.hip)
     // whole groups of eight samples: one sample of each group per XCD; the samples left over (B not a multiple of 8) are dealt out
     // item by item, round-robin over the XCDs (before round 3 they went to the first XCDs whole: B = 11 ran at 11/16)
     const int nb = H.B >> 3;                      // samples of the whole groups owned by this XCD
@@ -563,37 +594,74 @@ __device__ __forceinline__ void loss_body(const Hdr& H, const LossArgs& A) {
 }
 
 template <bool SSIM, bool GRAD, bool LOSS, bool EXPL, int SMODE, bool HWC, bool WARPED = false>
-__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, (SSIM && GRAD) ? 3 : 4) loss_kernel(SFM_HDR_PARAMS, const LossArgs A) {
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(Family::Base, SSIM, GRAD)) loss_kernel(SFM_HDR_PARAMS, const LossArgs A) {
   loss_body<SSIM, GRAD, LOSS, EXPL, SMODE, HWC, WARPED>(make_hdr(A, SFM_HDR_ARGS), A);
 }
 // (DSRC, see loss_body: the gradient kernels of a launch that also wants dL/d(src): the same kernels plus three stores per pixel row
 //  and source, the record of dL/dI^ that dsrc_scatter_kernel turns into d_src)
 template <bool SSIM, bool LOSS, bool EXPL, int SMODE, bool HWC, bool WARPED = false>
-__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, SSIM ? 3 : 4) loss_kernel_dsrc(SFM_HDR_PARAMS, const LossArgs A) {
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(Family::Dsrc, SSIM, true)) loss_kernel_dsrc(SFM_HDR_PARAMS, const LossArgs A) {
   loss_body<SSIM, true, LOSS, EXPL, SMODE, HWC, WARPED, 0, true>(make_hdr(A, SFM_HDR_ARGS), A);
 }
 // (REF, see loss_body: every launch of a descriptor with projection = SFM_PROJECTION_REFERENCE_ORDER; sfm_loss_ref.hip instantiates them)
 template <bool SSIM, bool GRAD, bool LOSS, bool EXPL, int SMODE, bool HWC, bool WARPED = false>
-__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, (SSIM && GRAD) ? 3 : 4) loss_kernel_ref(SFM_HDR_PARAMS, const LossArgs A) {
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(Family::Ref, SSIM, GRAD)) loss_kernel_ref(SFM_HDR_PARAMS, const LossArgs A) {
   // (DSRC = GRAD: these kernels record dL/dI^ whenever the descriptor binds d_src -- a run-time test of one pointer and three stores)
   loss_body<SSIM, GRAD, LOSS, EXPL, SMODE, HWC, WARPED, 1, GRAD>(make_hdr(A, SFM_HDR_ARGS), A);
 }
 // (PAIR, see loss_body: two sources per pass at two waves per SIMD; sfm_loss_pair.hip instantiates them)
 template <bool GRAD, bool LOSS, int SMODE>
-__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, 2) loss_kernel_pair(SFM_HDR_PARAMS, const LossArgs A) {
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(Family::Pair, true, GRAD)) loss_kernel_pair(SFM_HDR_PARAMS, const LossArgs A) {
   loss_body<true, GRAD, LOSS, false, SMODE, true, false, 0, false, true>(make_hdr(A, SFM_HDR_ARGS), A);
 }
 // (WIDE, see above: L1 gradient kernels only)
 template <bool LOSS, int SMODE, bool HWC, bool WARPED = false>
-__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, 3) loss_kernel_wide(SFM_HDR_PARAMS, const LossArgs A) {
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(Family::Wide, false, true)) loss_kernel_wide(SFM_HDR_PARAMS, const LossArgs A) {
   loss_body<false, true, LOSS, false, SMODE, HWC, WARPED>(make_hdr(A, SFM_HDR_ARGS), A);
 }
 
-
-// the kernel tables of the other translation units (sfm_loss_ref.hip, sfm_loss_dsrc.hip); nullptr = not built
-const void* kernel_ptr_ref(bool grad, bool loss, bool ssim, bool expl, int smode, bool hwc, bool warped);
-const void* kernel_ptr_dsrc(bool loss, bool ssim, bool expl, int smode, bool hwc, bool warped);
-const void* kernel_ptr_pair(bool grad, bool loss, int smode);
+// Which __global__ is family F's kernel for a set of template arguments; nullptr = the family has none.
+template <Family F, bool GRAD, bool LOSS, bool SSIM, bool EXPL, int SMODE, bool HWC, bool WARPED>
+const void* family_kernel() {
+  if constexpr (F == Family::Base) return (const void*)&loss_kernel<SSIM, GRAD, LOSS, EXPL, SMODE, HWC, WARPED>;
+  else if constexpr (F == Family::Ref) return (const void*)&loss_kernel_ref<SSIM, GRAD, LOSS, EXPL, SMODE, HWC, WARPED>;
+  else if constexpr (F == Family::Dsrc && GRAD) return (const void*)&loss_kernel_dsrc<SSIM, LOSS, EXPL, SMODE, HWC, WARPED>;
+  else if constexpr (F == Family::Wide && GRAD && !SSIM && !EXPL) return (const void*)&loss_kernel_wide<LOSS, SMODE, HWC, WARPED>;
+  // (the forward-only launches keep one source per pass: four waves per SIMD at 128 registers)
+  else if constexpr (F == Family::Pair && GRAD && SSIM && !EXPL && HWC && !WARPED) return (const void*)&loss_kernel_pair<GRAD, LOSS, SMODE>;
+  else return nullptr;
+}
+// The mode ladder, written once: lifts the run-time fields of a variant to template arguments, one rung per function.  A translation
+// unit instantiates it for its own families only (kernel_of_*), so each still compiles just its own kernels.
+template <Family F, bool GRAD, bool LOSS, bool SSIM, bool EXPL, int SMODE>
+const void* lift_layout(const Variant& v) {
+  if constexpr (LOSS) {      // (WARPED only exists for the LOSS entry points: those variants are not built elsewhere)
+    if (v.warped) return v.hwc ? family_kernel<F, GRAD, LOSS, SSIM, EXPL, SMODE, true, true>() : family_kernel<F, GRAD, LOSS, SSIM, EXPL, SMODE, false, true>();
+  }
+  return v.hwc ? family_kernel<F, GRAD, LOSS, SSIM, EXPL, SMODE, true, false>() : family_kernel<F, GRAD, LOSS, SSIM, EXPL, SMODE, false, false>();
+}
+template <Family F, bool GRAD, bool LOSS, bool SSIM, bool EXPL>
+const void* lift_smode(const Variant& v) {
+  if (v.smode == 0) return lift_layout<F, GRAD, LOSS, SSIM, EXPL, 0>(v);
+  if (v.smode == 1) return lift_layout<F, GRAD, LOSS, SSIM, EXPL, 1>(v);
+  return lift_layout<F, GRAD, LOSS, SSIM, EXPL, 2>(v);
+}
+template <Family F, bool GRAD, bool LOSS>
+const void* lift_mode(const Variant& v) {
+  if (v.expl) return lift_smode<F, GRAD, LOSS, false, true>(v);
+  if (v.ssim) return lift_smode<F, GRAD, LOSS, true, false>(v);
+  return lift_smode<F, GRAD, LOSS, false, false>(v);
+}
+template <Family F>
+const void* lift_variant(const Variant& v) {
+  if (v.grad && v.loss) return lift_mode<F, true, true>(v);
+  if (v.grad) return lift_mode<F, true, false>(v);
+  return lift_mode<F, false, true>(v);
+}
+// the kernels of the other translation units (sfm_loss_ref.hip, sfm_loss_dsrc.hip, sfm_loss_pair.hip)
+const void* kernel_of_ref(const Variant& v);
+const void* kernel_of_dsrc(const Variant& v);
+const void* kernel_of_pair(const Variant& v);
 
 // ------------------------------------------------------------------------------------------
 // The second launch of a call with SfmLossDesc.d_src bound (sfm_loss_dsrc.hip): dL/d(src) from the record of dL/dI^.

@@ -5,17 +5,6 @@
 
 namespace sfm {
 
-template <bool GRAD, bool LOSS>
-static const void* pick_pair(int smode) {
-  if (smode == 0) return (const void*)&loss_kernel_pair<GRAD, LOSS, 0>;
-  if (smode == 1) return (const void*)&loss_kernel_pair<GRAD, LOSS, 1>;
-  return (const void*)&loss_kernel_pair<GRAD, LOSS, 2>;
-}
-
-const void* kernel_ptr_pair(bool grad, bool loss, int smode) {
-  if (grad && loss) return pick_pair<true, true>(smode);
-  if (grad) return pick_pair<true, false>(smode);
-  return nullptr;     // (the forward-only launches keep one source per pass: four waves per SIMD at 128 registers)
-}
+const void* kernel_of_pair(const Variant& v) { return lift_variant<Family::Pair>(v); }
 
 }  // namespace sfm

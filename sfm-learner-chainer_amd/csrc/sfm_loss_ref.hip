@@ -7,36 +7,6 @@
 
 namespace sfm {
 
-template <bool GRAD, bool LOSS>
-static const void* pick_ref(bool ssim, bool expl, int smode, bool hwc, bool warped) {
-  // (WARPED only exists for the LOSS entry points)
-#define SFM_KPICK(...)                                                                                                              \
-  do {                                                                                                                              \
-    if constexpr (LOSS) {                                                                                                           \
-      if (warped) return hwc ? (const void*)&loss_kernel_ref<__VA_ARGS__, true, true> : (const void*)&loss_kernel_ref<__VA_ARGS__, false, true>; \
-    }                                                                                                                               \
-    return hwc ? (const void*)&loss_kernel_ref<__VA_ARGS__, true, false> : (const void*)&loss_kernel_ref<__VA_ARGS__, false, false>; \
-  } while (0)
-  if (expl) {
-    if (smode == 0) SFM_KPICK(false, GRAD, LOSS, true, 0);
-    else if (smode == 1) SFM_KPICK(false, GRAD, LOSS, true, 1);
-    else SFM_KPICK(false, GRAD, LOSS, true, 2);
-  } else if (ssim) {
-    if (smode == 0) SFM_KPICK(true, GRAD, LOSS, false, 0);
-    else if (smode == 1) SFM_KPICK(true, GRAD, LOSS, false, 1);
-    else SFM_KPICK(true, GRAD, LOSS, false, 2);
-  } else {
-    if (smode == 0) SFM_KPICK(false, GRAD, LOSS, false, 0);
-    else if (smode == 1) SFM_KPICK(false, GRAD, LOSS, false, 1);
-    else SFM_KPICK(false, GRAD, LOSS, false, 2);
-  }
-#undef SFM_KPICK
-}
-
-const void* kernel_ptr_ref(bool grad, bool loss, bool ssim, bool expl, int smode, bool hwc, bool warped) {
-  if (grad && loss) return pick_ref<true, true>(ssim, expl, smode, hwc, warped);
-  if (grad) return pick_ref<true, false>(ssim, expl, smode, hwc, warped);
-  return pick_ref<false, true>(ssim, expl, smode, hwc, warped);
-}
+const void* kernel_of_ref(const Variant& v) { return lift_variant<Family::Ref>(v); }
 
 }  // namespace sfm

@@ -897,7 +897,7 @@ def test_two_sources_per_pass_gives_the_one_source_results(ops, synth, dev, cfg_
     # the variants are two kernels with two plans: the pair form's chunks are taller, so it runs no more work items than the
     # one-source form (counted on the device) -- strictly fewer unless both are at the 4-row minimum chunk, which is where the count
     # cannot tell them apart (test_two_sources_per_pass_is_the_default_of_some_small_launch needs a shape where it can).  The
-    # default launch runs exactly what sfm_loss_plan_info reports, and that is one of the two (which one is make_plan's choice).
+    # default launch runs exactly what sfm_loss_plan_info reports, and that is one of the two (which one is choose_variant's choice).
     items = {v: traced_items(ops, fl, lambda: fl.forward_backward(variant=v)) for v in (4, 5)}
     default = traced_items(ops, fl, fl.forward_backward)
     planned = planned_items(ops, fl, 1, 1)
@@ -911,7 +911,7 @@ def test_two_sources_per_pass_gives_the_one_source_results(ops, synth, dev, cfg_
 def test_two_sources_per_pass_is_the_default_of_some_small_launch(ops, synth, dev, cfg_name):
     """What the pair-form test above cannot see from one shape: over its shapes, at least one default launch (a small batch) IS the
     two-sources-per-pass launch -- the traced item count of the default equals that of sfm_loss_variant(5) and is below that of
-    (4), so the hook really switched the kernel.  Which shapes do is left to make_plan."""
+    (4), so the hook really switched the kernel.  Which shapes do is left to choose_variant (sfm_loss.hip)."""
     taken = []
     for shape in PAIR_SHAPES:
         B, H, W, n_src, n_scales = shape
