@@ -168,7 +168,10 @@ typedef struct SfmLossDesc {
   const float *src[SFM_MAX_SCALES];         /* (B,3*n_src,h,w)  curr_src_imgs (:72)  [layout] */
   const float *disp[SFM_MAX_SCALES];        /* (B,1,h,w)        pred_disps    (:59)           */
   const float *mask_logits[SFM_MAX_SCALES]; /* (B,n_src,h,w)    pred_maskes (:62) or NULL     */
-  const float *intrinsics;                  /* (B,n_scales,3,3) (:85)                         */
+  const float *intrinsics;                  /* (B,n_scales,3,3) (:85): ANY invertible 3x3 per (sample, scale) -- skew, a general
+                                             * bottom row, a scaled matrix -- and the scales need not be related (scale s is read, never
+                                             * derived from scale 0); all nine entries are used, as by F.batch_inv / F.batch_matmul
+                                             * (transform.py:43-91,105).  Held by tests/test_cameras_gpu.py.                            */
   const float *pose[SFM_MAX_SRC];           /* (B,6)            pred_poses[i] (:62)           */
   /* gradient outputs (backward only) */
   float *d_disp[SFM_MAX_SCALES]; /* (B,1,h,w)     overwritten                                 */

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import cameras
 from oracle import sfm_oracle as O
 from oracle.parity import rel_l2
 from util import assert_close_masked, parity_note, to_dev, to_np
@@ -53,17 +54,8 @@ def test_pose_proj_matches_oracle_and_odom_util_golden(ops, dev):
 WARP_TOL = 1e-4      # north_star: warped pixels within 1e-4 of the reference (relative to the image range), on EVERY texture
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 16, 52), (1, 3, 37, 70), (2, 1, 9, 11), (1, 5, 128, 416), (2, 3, 128, 416)])
-@pytest.mark.parametrize("texture", ["smooth", "noise"])
-@pytest.mark.parametrize("depth_rows", [1, 3])
-def test_projective_inverse_warp_fwd_bwd(ops, synth, dev, shape, texture, depth_rows):
-    """projective_inverse_warp (models/transform.py:156-193).  The operator keeps the reference's evaluation order
-    (Pm . (D . K^-1 . pix, 1), +1e-10, normalise, x2, the sampler's de-normalisation; no fused multiply-adds), so:
-      * warped pixels agree with the oracle to 1e-4 of the image range on image-like AND white-noise sources, at every
-        pixel -- no knife-edge exclusion;
-      * the set of exactly-zero (out-of-view) pixels is the oracle's, pixel for pixel;
-      * the backward is compared with the oracle's hand-derived one (element-wise outside the pixels whose sample sits on
-        a cell boundary of the bilinear lattice, where dI^/du itself jumps; their share is printed and bounded)."""
+def warp_inputs(synth, shape, texture, depth_rows, kind=None):
+    """The inputs of the warp operator's parity tests; `kind`: intrinsics from cameras.cameras instead of synth's."""
     N, C, H, W = shape
     d = synth.make_inputs(B=N, H=H, W=W, n_src=2, n_scales=1, seed=4)
     rng = np.random.RandomState(1)
@@ -79,7 +71,15 @@ def test_projective_inverse_warp_fwd_bwd(ops, synth, dev, shape, texture, depth_
     else:                    # one row of the reference's broadcast (base_model.py:82-84)
         depthes = np.broadcast_to(depth[:, None], (N, 3, H * W))
         dev_depth = depth
-    pose, K = d["poses"][0], d["intrinsics"][:, 0]
+    if kind is not None:
+        d = cameras.with_cameras(d, kind, 1004)
+    return dict(imgs=imgs, depthes=depthes, dev_depth=dev_depth, pose=d["poses"][0], K=d["intrinsics"][:, 0], rng=rng)
+
+
+def check_warp_fwd_bwd(ops, dev, inp, shape, texture, depth_rows):
+    """the body of test_projective_inverse_warp_fwd_bwd on the inputs `inp` (warp_inputs)"""
+    N, C, H, W = shape
+    imgs, depthes, dev_depth, pose, K, rng = (inp[k] for k in ("imgs", "depthes", "dev_depth", "pose", "K", "rng"))
     want, aux = O.projective_inverse_warp(imgs, depthes, pose, K, return_aux=True)
     targs = [to_dev(a, dev) for a in (imgs, dev_depth, pose, K)]
     got = to_np(ops.warp_fwd(*targs))
@@ -118,6 +118,20 @@ def test_projective_inverse_warp_fwd_bwd(ops, synth, dev, shape, texture, depth_
         assert pose_err <= max(2e-3, 3 * own_err) and pose_l2 <= max(1e-3, 3 * own_l2), (pose_err, pose_l2, own_err, own_l2)
     parity_note("warp_bwd %s %s rows=%d: d_pose max element-wise %.2e (tol 2e-3), relative L2 %.2e (tol 1e-3)" % (shape, texture, depth_rows, pose_err, pose_l2))
     assert_close_masked(to_np(d_src), w_src, 2e-3, None, what="d_src")
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 16, 52), (1, 3, 37, 70), (2, 1, 9, 11), (1, 5, 128, 416), (2, 3, 128, 416)])
+@pytest.mark.parametrize("texture", ["smooth", "noise"])
+@pytest.mark.parametrize("depth_rows", [1, 3])
+def test_projective_inverse_warp_fwd_bwd(ops, synth, dev, shape, texture, depth_rows):
+    """projective_inverse_warp (models/transform.py:156-193).  The operator keeps the reference's evaluation order
+    (Pm . (D . K^-1 . pix, 1), +1e-10, normalise, x2, the sampler's de-normalisation; no fused multiply-adds), so:
+      * warped pixels agree with the oracle to 1e-4 of the image range on image-like AND white-noise sources, at every
+        pixel -- no knife-edge exclusion;
+      * the set of exactly-zero (out-of-view) pixels is the oracle's, pixel for pixel;
+      * the backward is compared with the oracle's hand-derived one (element-wise outside the pixels whose sample sits on
+        a cell boundary of the bilinear lattice, where dI^/du itself jumps; their share is printed and bounded)."""
+    check_warp_fwd_bwd(ops, dev, warp_inputs(synth, shape, texture, depth_rows), shape, texture, depth_rows)
 
 
 @pytest.mark.parametrize("shape", [(2, 3, 8, 13, 8, 13), (1, 2, 5, 7, 11, 3), (2, 3, 16, 52, 16, 52), (1, 6, 9, 70, 35, 67), (1, 4, 40, 9, 33, 130)])

@@ -23,7 +23,11 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+import cameras
+import test_loss_gpu as L      # its constants and knife widths (nothing in it runs here)
+import test_ops_gpu as OPS     # the inputs of its warp test
 from oracle import sfm_oracle as O
+from oracle.parity import knife_mask
 
 TOL = 1e-10
 DT = torch.float64
@@ -143,22 +147,20 @@ CONFIGS = {
 }
 
 
-@pytest.mark.parametrize("name", sorted(CONFIGS))
-@pytest.mark.parametrize("shape", [(2, 24, 40, 2, 2), (1, 17, 29, 3, 3)])
-def test_oracle_loss_and_gradients_match_torch_autograd(synth, name, shape):
-    B, H, W, n_src, n_scales = shape
-    cfg = CONFIGS[name]
-    d = synth.make_inputs(B=B, H=H, W=W, n_src=n_src, n_scales=n_scales, seed=31, with_masks=True)
-    # larger motion than the synthetic default, so that a good share of the pixels leaves the view (zero fill, x2 rule, mask)
-    rng = np.random.RandomState(5)
-    d["poses"] = [p + rng.normal(0, 0.03, p.shape).astype(np.float32) * np.array([1, 1, 1, 4, 4, 4], np.float32) for p in d["poses"]]
+def _compare_with_autograd(d, cfg, with_src=False):
+    """The fp64 oracle against torch autograd on the inputs d: the five scalars, d_disp, d_pose, d_mask (explainability modes) and,
+    `with_src`, d_srcs against the gradient of the source pyramid taken as a leaf -- everything at TOL, nothing excluded.  (d_srcs
+    can only be compared without a mask on inputs free of exact ties I^ == I, where sign(0) is a convention: asserted from the
+    oracle's `abs_zero`.)  Returns the oracle's result."""
     ref = O.sfm_loss(d["tgt_pyr"], d["src_pyr"], d["intrinsics"], d["disps"], d["poses"], d["masks"], backward=True,
-                     dtype=np.float64, keep_warped=True, **cfg)
+                     dtype=np.float64, keep_warped=True, want_d_src=with_src, **cfg)
+    n_scales, n_src = len(d["disps"]), len(d["poses"])
     t = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64))
     disps = [t(a).requires_grad_(True) for a in d["disps"]]
     poses = [t(a).requires_grad_(True) for a in d["poses"]]
     masks = [t(a).requires_grad_(True) for a in d["masks"]]
-    out = torch_loss([t(a) for a in d["tgt_pyr"]], [t(a) for a in d["src_pyr"]], t(d["intrinsics"]), disps, poses, masks, **cfg)
+    srcs = [t(a).requires_grad_(with_src) for a in d["src_pyr"]]
+    out = torch_loss([t(a) for a in d["tgt_pyr"]], srcs, t(d["intrinsics"]), disps, poses, masks, **cfg)
     out[0].backward()
     for got, key in zip(out, ("total_loss", "pixel_loss", "smooth_loss", "exp_loss", "ssim_loss")):
         assert abs(float(got.detach()) - ref[key]) <= TOL * max(abs(ref[key]), 1e-12), (key, float(got.detach()), ref[key])
@@ -174,8 +176,151 @@ def test_oracle_loss_and_gradients_match_torch_autograd(synth, name, shape):
         close(disps[s].grad, ref["d_disps"][s], "d_disp[%d]" % s)
         if cfg.get("exp_reg"):
             close(masks[s].grad, ref["d_masks"][s], "d_mask[%d]" % s)
+        if with_src:
+            assert not ref["abs_zero"][s].any(), "scale %d: %d in-view pixels with I^ == I exactly" % (s, int(ref["abs_zero"][s].sum()))
+            assert np.abs(ref["d_srcs"][s]).max() > 0
+            close(srcs[s].grad, ref["d_srcs"][s], "d_src[%d]" % s)
     for i in range(n_src):
         close(poses[i].grad, ref["d_poses"][i], "d_pose[%d]" % i)
+    return ref
+
+
+@pytest.mark.parametrize("name", sorted(CONFIGS))
+@pytest.mark.parametrize("shape", [(2, 24, 40, 2, 2), (1, 17, 29, 3, 3)])
+def test_oracle_loss_and_gradients_match_torch_autograd(synth, name, shape):
+    B, H, W, n_src, n_scales = shape
+    cfg = CONFIGS[name]
+    d = synth.make_inputs(B=B, H=H, W=W, n_src=n_src, n_scales=n_scales, seed=31, with_masks=True)
+    # larger motion than the synthetic default, so that a good share of the pixels leaves the view (zero fill, x2 rule, mask)
+    rng = np.random.RandomState(5)
+    d["poses"] = [p + rng.normal(0, 0.03, p.shape).astype(np.float32) * np.array([1, 1, 1, 4, 4, 4], np.float32) for p in d["poses"]]
+    _compare_with_autograd(d, cfg)
+
+
+def tie_free(d, seed=77):
+    """d with the target pyramid moved off the sources' values (x 0.97 + 0.01 N(0,1)): synth's saturated +-1 regions otherwise put
+    I^ == I exactly at in-view pixels, where d_src depends on the convention sign(0) = 0 (tests/test_loss_gpu.py: src_footprints)."""
+    rng = np.random.RandomState(seed)
+    return dict(d, tgt_pyr=[(a * 0.97 + 0.01 * rng.standard_normal(a.shape)).astype(np.float32) for a in d["tgt_pyr"]])
+
+
+CAMERA_SHAPE = (2, 32, 48, 2, 3)
+
+
+@pytest.mark.parametrize("name", cameras.MODES)
+@pytest.mark.parametrize("kind", cameras.KINDS)
+def test_oracle_matches_torch_autograd_on_general_cameras(synth, kind, name):
+    """The oracle is the yardstick of tests/test_cameras_gpu.py: here it is held against autograd for intrinsics that are not
+    [[fx,0,cx],[0,fy,cy],[0,0,1]] (skew, a general bottom row, scales that are not scale 0 over 2**s, a scaled matrix), d_srcs
+    included."""
+    d = tie_free(cameras.camera_inputs(synth, CAMERA_SHAPE, kind))
+    _compare_with_autograd(d, CONFIGS[name], with_src=True)
+
+
+@pytest.mark.parametrize("name", cameras.MODES)
+@pytest.mark.parametrize("kind", [None, "general"])
+def test_oracle_matches_torch_autograd_on_exact_zero_pixels(synth, kind, name):
+    """Images with exact zeros (cameras.zero_regions): samples that are IN VIEW and masked because all three warped channels are 0
+    (models/base_model.py:96), next to regions with ONE zero channel, which must not be -- with synth's cameras and general ones."""
+    d, rect, one_src, one_tgt = cameras.zero_regions(tie_free(cameras.camera_inputs(synth, CAMERA_SHAPE, kind)))
+    ref = _compare_with_autograd(d, CONFIGS[name], with_src=True)
+    for s, share in enumerate(zero_pixel_shares(d, ref, one_src, one_tgt)):
+        assert share >= 0.03, (s, share)
+
+
+def in_view(d, ref, s):
+    """(B,n,h,w): the sampling position of the oracle passes the strict test of models/transform.py:129"""
+    h, w = d["disps"][s].shape[2:]
+    with np.errstate(invalid="ignore"):
+        xn, yn = ref["uv"][s][:, :, 0] / ((w - 1) / 2.) - 1, ref["uv"][s][:, :, 1] / ((h - 1) / 2.) - 1
+        return (xn > -1) & (xn < 1) & (yn > -1) & (yn < 1)
+
+
+def zero_pixel_shares(d, ref, one_src, one_tgt):
+    """Per scale, the share of the (sample, source, pixel) triples that are in view AND masked (all three warped channels exactly
+    0); asserts on the way that a zero in ONE channel masks nothing: no in-view pixel of the target's one-channel region, and no
+    in-view pixel whose four taps all lie in the sources' one-channel region, is masked."""
+    shares = []
+    for s, w in enumerate(ref["warped"]):
+        inv = in_view(d, ref, s)
+        masked = (w == 0).all(axis=2)
+        assert not (masked & inv & one_tgt[s]).any(), "scale %d: masked in-view pixels inside the target's one-channel region" % s
+        hh, ww = one_src[s].shape
+        with np.errstate(invalid="ignore"):
+            u0 = np.clip(np.nan_to_num(np.floor(ref["uv"][s][:, :, 0])), 0, ww - 2).astype(np.int64)
+            v0 = np.clip(np.nan_to_num(np.floor(ref["uv"][s][:, :, 1])), 0, hh - 2).astype(np.int64)
+        a = one_src[s]
+        taps_in = a[v0, u0] & a[v0, u0 + 1] & a[v0 + 1, u0] & a[v0 + 1, u0 + 1]
+        assert (taps_in & inv).any(), "scale %d: no in-view sample inside the sources' one-channel region" % s
+        assert not (masked & inv & taps_in).any(), "scale %d: masked in-view pixels whose taps lie in the sources' one-channel region" % s
+        shares.append(float((masked & inv).mean()))
+    return shares
+
+
+def _knife(d, ref, s):
+    """the pixels test_loss_gpu._check_grads excludes from the element-wise comparison of d_disp[s], with the widths
+    tests/test_cameras_gpu.py passes (knife_widths)"""
+    kw = L.knife_widths(d, ref)
+    return knife_mask(ref, s, cell_thr=kw["cell_thr"](s), abs_thr=kw["abs_thr"](s))[0][:, None]
+
+
+def visible_difference(d, ref, other):
+    """By how many times its tolerance the result `other` misses the comparison tests/test_loss_gpu.py would make against `ref`
+    (both from the fp32 oracle on the inputs d, `other` with another K): the larger of (a) the relative difference of a loss scalar
+    over LOSS_RTOL and (b) the largest difference of d_disp over GRAD_TOL of its maximum, at pixels outside the knife mask of BOTH
+    evaluations (a kernel that computed `other` is compared outside ref's mask; outside both, neither side sits on a discontinuity)."""
+    loss = max(abs(other[k] - ref[k]) / max(abs(ref[k]), 1e-6) for k in L.KEYS) / L.LOSS_RTOL
+    grad = 0.0
+    for s, (a, b) in enumerate(zip(other["d_disps"], ref["d_disps"])):
+        keep = ~(_knife(d, ref, s) | _knife(d, other, s))
+        grad = max(grad, float((np.abs(a.astype(np.float64) - b) * keep).max() / np.abs(b).max()) / L.GRAD_TOL)
+    return loss, grad
+
+
+def _oracle32(d, cfg):
+    return O.sfm_loss(d["tgt_pyr"], d["src_pyr"], d["intrinsics"], d["disps"], d["poses"], d["masks"], backward=True, keep_warped=True, **cfg)
+
+
+@pytest.mark.parametrize("shape,zeros,kind", [(shape, False, kind) for shape in cameras.CASES for kind in cameras.KINDS]
+                         + [(CAMERA_SHAPE, True, "general")])
+def test_a_kernel_that_ignored_an_entry_of_K_would_fail(synth, shape, zeros, kind):
+    """What makes tests/test_cameras_gpu.py a test of the general 3x3: on its exact inputs (shapes, seeds, loss modes; `True`: with
+    the exact-zero regions), a result computed with one entry of K ignored -- K01, K10, K20, K21 taken as 0, K22 as 1, the scales
+    rebuilt from scale 0, or K divided by K22 -- differs from the right one by at least TEN times a tolerance the GPU tests apply:
+    LOSS_RTOL on a loss scalar or GRAD_TOL of the maximum on d_disp outside the knife mask.  Both sides are the fp32 oracle.
+    The table of which ablation can show on which kind (cameras.ABLATIONS_OF) is checked too: an ablation that is not listed
+    leaves that kind's K bit for bit as it is."""
+    d = cameras.camera_inputs(synth, shape, kind, zeros=zeros)
+    K = d["intrinsics"]
+    for name, ablate in cameras.ABLATIONS.items():
+        if name not in cameras.ABLATIONS_OF[kind]:
+            np.testing.assert_array_equal(ablate(K), K, err_msg="%s changes the %s cameras: list it" % (name, kind))
+    for mode in (cameras.MODES if kind == "general" else (cameras.MODE_OF[kind],)):
+        cfg = CONFIGS[mode]
+        ref = _oracle32(d, cfg)
+        for name in cameras.ABLATIONS_OF[kind]:
+            Ka = np.ascontiguousarray(cameras.ABLATIONS[name](K), dtype=np.float32)
+            assert Ka.shape == K.shape and not np.array_equal(Ka, K)
+            loss, grad = visible_difference(d, ref, _oracle32(dict(d, intrinsics=Ka), cfg))
+            print("%s %s %s %s: loss off by %.1f x LOSS_RTOL, d_disp by %.1f x GRAD_TOL" % (shape, kind, mode, name, loss, grad))
+            assert max(loss, grad) >= 10.0, (shape, kind, mode, name, loss, grad)
+
+
+@pytest.mark.parametrize("kind", ["skew", "bottom", "scaled", "general"])
+@pytest.mark.parametrize("shape", [(2, 3, 16, 52), (1, 3, 37, 70)])
+def test_a_warp_operator_that_ignored_an_entry_of_K_would_fail(synth, shape, kind):
+    """The same for the inputs of test_cameras_gpu.test_projective_inverse_warp_on_general_cameras: with one entry of K ignored
+    the oracle's warped image moves by at least ten times that test's 1e-4 at a pixel both evaluations sample -- on the white-noise
+    texture of that test (on the smooth one K20 moves the pixels by 8e-4 only: there the backward's comparisons would notice)."""
+    inp = OPS.warp_inputs(synth, shape, "noise", 1, kind)
+    imgs, depthes, pose, K = inp["imgs"], inp["depthes"], inp["pose"], inp["K"][:, None]
+    want = O.projective_inverse_warp(imgs, depthes, pose, K[:, 0])
+    for name in cameras.ABLATIONS_OF[kind]:
+        if name == "scales rebuilt from scale 0":      # the operator sees one scale
+            continue
+        other = O.projective_inverse_warp(imgs, depthes, pose, cameras.ABLATIONS[name](K)[:, 0])
+        both = ~(want == 0).all(1, keepdims=True) & ~(other == 0).all(1, keepdims=True)
+        assert (np.abs(other - want) * both).max() >= 10 * 1e-4, (shape, kind, name, float((np.abs(other - want) * both).max()))
 
 
 def test_oracle_sampler_matches_grid_sample():
