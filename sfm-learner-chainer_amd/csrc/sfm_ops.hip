@@ -16,17 +16,19 @@ namespace sfm {
 
 static thread_local char g_err[512] = "";
 
+static void set_error_v(const char* fmt, va_list ap) { vsnprintf(g_err, sizeof(g_err), fmt, ap); }
+
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  set_error_v(fmt, ap);
   va_end(ap);
 }
 
 int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  set_error_v(fmt, ap);
   va_end(ap);
   return code;
 }
@@ -510,25 +512,65 @@ __global__ void interp_bwd_kernel(const float* __restrict__ x, const float* __re
 }
 
 // ------------------------------------------------------------------------------------------
-// F.resize_images, align-corners bilinear (models/base_model.py:70-72)
+// F.resize_images, align-corners bilinear (models/base_model.py:70-72).  Source coordinate, taps and weights, and the blend are
+// these functions for every kernel that resamples (resize, the three pyramid kernels, augment): that their values agree bit for
+// bit is a property of the code (one exception: pyramid_hwc_fwd_kernel writes the blend out, see there).  Each carries its own
+// contract(off): the pragma is lexical and does not follow the caller.
 // ------------------------------------------------------------------------------------------
+struct ResizeTap {
+  int u0, u1, v0, v1;
+  float wu0, wu1, wv0, wv1;
+};
+
+// numpy.linspace(0, W-1, oW)[o] = o * step with step = (W-1)/(oW-1), evaluated in double (o: an output index, converted by the call)
+__device__ __forceinline__ float resize_coord(const double o, const double step) {
+#pragma clang fp contract(off)
+  return (float)(o * step);
+}
+
+__device__ __forceinline__ int resize_tap0(const float x, const int n) { return min(max((int)floorf(x), 0), max(n - 2, 0)); }
+
+__device__ __forceinline__ ResizeTap resize_taps(const float u, const float v, const int H, const int W) {
+#pragma clang fp contract(off)
+  ResizeTap t;
+  t.u0 = resize_tap0(u, W), t.v0 = resize_tap0(v, H);
+  t.u1 = min(t.u0 + 1, W - 1), t.v1 = min(t.v0 + 1, H - 1);
+  t.wu1 = u - (float)t.u0, t.wv1 = v - (float)t.v0;
+  t.wu0 = 1.0f - t.wu1, t.wv0 = 1.0f - t.wv1;
+  return t;
+}
+
+// a0 a1 / b0 b1: the values at (v0, u0) (v0, u1) / (v1, u0) (v1, u1), however the caller fetched them
+__device__ __forceinline__ float resize_blend(const ResizeTap& t, const float a0, const float a1, const float b0, const float b1) {
+#pragma clang fp contract(off)
+  const float top = a0 * t.wu0 + a1 * t.wu1;
+  const float bot = b0 * t.wu0 + b1 * t.wu1;
+  return top * t.wv0 + bot * t.wv1;
+}
+
+__device__ __forceinline__ float resize_read(const ResizeTap& t, const float* img, const int W) {
+  return resize_blend(t, img[t.v0 * W + t.u0], img[t.v0 * W + t.u1], img[t.v1 * W + t.u0], img[t.v1 * W + t.u1]);
+}
+
+// the scale a flat index over several scales belongs to: the last s >= FIRST with j >= begin[s]
+template <int FIRST, typename Index>
+__device__ __forceinline__ int scale_of(const Index j, const Index* begin, const int n_scales) {
+  int s = FIRST;
+#pragma unroll
+  for (int k = FIRST + 1; k < SFM_MAX_SCALES; ++k)
+    if (k < n_scales && j >= begin[k]) s = k;
+  return s;
+}
+
 __global__ void resize_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int oH, int oW) {
 #pragma clang fp contract(off)
   const int nc = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= oH * oW) return;
   const int oy = j / oW, ox = j - oy * oW;
-  // numpy.linspace(0, W-1, oW)[ox] = ox * step with step = (W-1)/(oW-1), evaluated in double
-  const float u = oW > 1 ? (float)((double)ox * ((double)(W - 1) / (double)(oW - 1))) : 0.f;
-  const float v = oH > 1 ? (float)((double)oy * ((double)(H - 1) / (double)(oH - 1))) : 0.f;
-  const int u0 = min(max((int)floorf(u), 0), max(W - 2, 0)), v0 = min(max((int)floorf(v), 0), max(H - 2, 0));
-  const int u1 = min(u0 + 1, W - 1), v1 = min(v0 + 1, H - 1);
-  const float wu1 = u - (float)u0, wv1 = v - (float)v0;
-  const float wu0 = 1.0f - wu1, wv0 = 1.0f - wv1;
-  const float* img = x + (size_t)nc * H * W;
-  const float top = img[v0 * W + u0] * wu0 + img[v0 * W + u1] * wu1;
-  const float bot = img[v1 * W + u0] * wu0 + img[v1 * W + u1] * wu1;
-  y[(size_t)nc * oH * oW + j] = top * wv0 + bot * wv1;
+  const float u = oW > 1 ? resize_coord(ox, (double)(W - 1) / (double)(oW - 1)) : 0.f;
+  const float v = oH > 1 ? resize_coord(oy, (double)(H - 1) / (double)(oH - 1)) : 0.f;
+  y[(size_t)nc * oH * oW + j] = resize_read(resize_taps(u, v, H, W), x + (size_t)nc * H * W, W);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -552,41 +594,22 @@ struct PyramidArgs {
   int quads0;                    // HWC forms: threads of scale 0, four pixels each (ceil(H W / 4))
 };
 
-static void pyramid_steps(PyramidArgs& A) {
-  for (int s = 0; s < A.n_scales; ++s) {
-    A.step_u[s] = A.oW[s] > 1 ? (double)(A.W - 1) / (double)(A.oW[s] - 1) : 0.0;
-    A.step_v[s] = A.oH[s] > 1 ? (double)(A.H - 1) / (double)(A.oH[s] - 1) : 0.0;
-    A.inv_oW[s] = 1.0f / (float)A.oW[s];
-  }
-}
-
 __global__ void pyramid_fwd_kernel(const PyramidArgs A) {
 #pragma clang fp contract(off)
   const int nc = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.begin[A.n_scales]) return;
-  int s = 1;
-#pragma unroll
-  for (int k = 2; k < SFM_MAX_SCALES; ++k)
-    if (k < A.n_scales && j >= A.begin[k]) s = k;
+  const int s = scale_of<1>(j, A.begin, A.n_scales);
   const int jj = j - A.begin[s];
   const int oW = A.oW[s], oH = A.oH[s], H = A.H, W = A.W;
   const int oy = jj / oW, ox = jj - oy * oW;
-  const float u = (float)((double)ox * A.step_u[s]);
-  const float v = (float)((double)oy * A.step_v[s]);
-  const int u0 = min(max((int)floorf(u), 0), max(W - 2, 0)), v0 = min(max((int)floorf(v), 0), max(H - 2, 0));
-  const int u1 = min(u0 + 1, W - 1), v1 = min(v0 + 1, H - 1);
-  const float wu1 = u - (float)u0, wv1 = v - (float)v0;
-  const float wu0 = 1.0f - wu1, wv0 = 1.0f - wv1;
-  const float* img = A.x + (size_t)nc * H * W;
-  const float top = img[v0 * W + u0] * wu0 + img[v0 * W + u1] * wu1;
-  const float bot = img[v1 * W + u0] * wu0 + img[v1 * W + u1] * wu1;
-  A.y[s][(size_t)nc * oH * oW + jj] = top * wv0 + bot * wv1;
+  const ResizeTap t = resize_taps(resize_coord(ox, A.step_u[s]), resize_coord(oy, A.step_v[s]), H, W);
+  A.y[s][(size_t)nc * oH * oW + jj] = resize_read(t, A.x + (size_t)nc * H * W, W);
 }
 
 // The same pyramid, pixel-interleaved (SFM_LAYOUT_HWC): x (N,3G,H,W) -> y[s] (N,G,h_s,w_s,3), s = 0..S-1.  One thread
-// per output pixel computes the three channels with one set of weights; per channel the arithmetic is that of
-// pyramid_fwd_kernel, so the values agree bit for bit.  Scale 0 is a copy.
+// per output pixel computes the three channels with one set of weights: coordinate, taps and weights are resize_coord / resize_taps
+// as in pyramid_fwd_kernel, the blend is resize_blend's three statements, so the values agree bit for bit.  Scale 0 is a copy.
 struct __attribute__((packed, aligned(4))) Pair2 {    // two horizontally adjacent pixels of a plane
   float a, b;
 };
@@ -641,7 +664,8 @@ __global__ void pyramid_hwc_fwd_kernel(const PyramidArgs A) {
     }
     return;
   }
-  int s = 1;
+  int s = 1;   // (scale_of<1> and, below, resize_blend written out: through the helpers the compiler orders the same operations of
+               //  THIS kernel differently, and its code was to stay what it was)
 #pragma unroll
   for (int k = 2; k < SFM_MAX_SCALES; ++k)
     if (k < A.n_scales && j >= A.begin[k]) s = k;
@@ -658,29 +682,24 @@ __global__ void pyramid_hwc_fwd_kernel(const PyramidArgs A) {
     oy = jj / oW;
     ox = jj - oy * oW;
   }
-  const float u = (float)((double)ox * A.step_u[s]);
-  const float v = (float)((double)oy * A.step_v[s]);
-  const int u0 = min(max((int)floorf(u), 0), max(W - 2, 0)), v0 = min(max((int)floorf(v), 0), max(H - 2, 0));
-  const int u1 = min(u0 + 1, W - 1), v1 = min(v0 + 1, H - 1);
-  const float wu1 = u - (float)u0, wv1 = v - (float)v0;
-  const float wu0 = 1.0f - wu1, wv0 = 1.0f - wv1;
+  const ResizeTap tap = resize_taps(resize_coord(ox, A.step_u[s]), resize_coord(oy, A.step_v[s]), H, W);
   Float3 t;
   if (W >= 2) {   // u1 = u0 + 1: the two taps of a row with one 8-byte load
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float* pl = img + c * P;
-      const Pair2 a = *reinterpret_cast<const Pair2*>(pl + v0 * W + u0), b = *reinterpret_cast<const Pair2*>(pl + v1 * W + u0);
-      const float top = a.a * wu0 + a.b * wu1;
-      const float bot = b.a * wu0 + b.b * wu1;
-      t.c[c] = top * wv0 + bot * wv1;
+      const Pair2 a = *reinterpret_cast<const Pair2*>(pl + tap.v0 * W + tap.u0), b = *reinterpret_cast<const Pair2*>(pl + tap.v1 * W + tap.u0);
+      const float top = a.a * tap.wu0 + a.b * tap.wu1;
+      const float bot = b.a * tap.wu0 + b.b * tap.wu1;
+      t.c[c] = top * tap.wv0 + bot * tap.wv1;
     }
   } else {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float* pl = img + c * P;
-      const float top = pl[v0 * W + u0] * wu0 + pl[v0 * W + u1] * wu1;
-      const float bot = pl[v1 * W + u0] * wu0 + pl[v1 * W + u1] * wu1;
-      t.c[c] = top * wv0 + bot * wv1;
+      const float top = pl[tap.v0 * W + tap.u0] * tap.wu0 + pl[tap.v0 * W + tap.u1] * tap.wu1;
+      const float bot = pl[tap.v1 * W + tap.u0] * tap.wu0 + pl[tap.v1 * W + tap.u1] * tap.wu1;
+      t.c[c] = top * tap.wv0 + bot * tap.wv1;
     }
   }
   *reinterpret_cast<Float3*>(yout[s] + ((size_t)ng * oH * oW + jj) * 3) = t;
@@ -690,17 +709,15 @@ __global__ void pyramid_hwc_fwd_kernel(const PyramidArgs A) {
 // one row below) into LDS with 16-byte loads, writes the band's own rows of scale 0 (the planar -> pixel-interleaved
 // transposition) and every output row of the smaller scales whose upper tap row v0 lies in the band (then v0 + 1 is in LDS too).
 // pyramid_hwc_fwd_kernel fetches the input once per scale -- 2.75x the image in cache lines at four scales, from other XCDs' L2.
-// Per output pixel the arithmetic is that kernel's, statement by statement: the values agree bit for bit.
+// Per output pixel the arithmetic is that kernel's -- resize_coord, resize_taps, resize_blend -- so the values agree bit for bit.
 struct BandArgs {
   PyramidArgs P;
   int band_rows;      // input rows per band (the LDS holds band_rows + 1 rows of three planes)
   int n_bands;
 };
 
-__device__ __forceinline__ int pyr_v0(const PyramidArgs& A, const int s, const int oy) {
-#pragma clang fp contract(off)
-  const float v = (float)((double)oy * A.step_v[s]);
-  return min(max((int)floorf(v), 0), max(A.H - 2, 0));
+__device__ __forceinline__ int pyr_v0(const PyramidArgs& A, const int s, const int oy) {   // the upper tap row of output row oy
+  return resize_tap0(resize_coord(oy, A.step_v[s]), A.H);
 }
 
 template <bool PAIR, int NT>
@@ -775,21 +792,13 @@ __global__ void __launch_bounds__(NT) pyramid_band_hwc_kernel(const BandArgs B) 
     const int cnt = (hi - lo) * oW;
     for (int idx = tid; idx < cnt; idx += NT) {
       const int dy = idx / oW, ox = idx - dy * oW, oy = lo + dy;
-      const float u = (float)((double)ox * A.step_u[s]);
-      const float v = (float)((double)oy * A.step_v[s]);
-      const int u0 = min(max((int)floorf(u), 0), max(W - 2, 0)), v0 = min(max((int)floorf(v), 0), max(H - 2, 0));
-      const int v1 = min(v0 + 1, H - 1);
-      const float wu1 = u - (float)u0, wv1 = v - (float)v0;
-      const float wu0 = 1.0f - wu1, wv0 = 1.0f - wv1;
+      const ResizeTap tap = resize_taps(resize_coord(ox, A.step_u[s]), resize_coord(oy, A.step_v[s]), H, W);
+      const int a = (tap.v0 - r0) * W + tap.u0, b = (tap.v1 - r0) * W + tap.u0;      // (W >= 2 for this kernel: u1 = u0 + 1)
       Float3 t;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float* pl = band + c * span;
-        const float a0 = pl[(v0 - r0) * W + u0], a1 = pl[(v0 - r0) * W + u0 + 1];     // (W >= 2 for this kernel: u1 = u0 + 1)
-        const float b0 = pl[(v1 - r0) * W + u0], b1 = pl[(v1 - r0) * W + u0 + 1];
-        const float top = a0 * wu0 + a1 * wu1;
-        const float bot = b0 * wu0 + b1 * wu1;
-        t.c[c] = top * wv0 + bot * wv1;
+        t.c[c] = resize_blend(tap, pl[a], pl[a + 1], pl[b], pl[b + 1]);
       }
       *reinterpret_cast<Float3*>(yout[s] + ((size_t)ng * oH * oW + (size_t)oy * oW + ox) * 3) = t;
     }
@@ -810,7 +819,6 @@ static const PyramidTuning& pyramid_tuning() { static const PyramidTuning t; ret
 // sfm_pyramid_variant(): which kernel the NEXT pixel-interleaved pyramid call of this thread runs (then back to 0 = automatic)
 static thread_local int g_pyramid_variant = 0;
 
-// Launches the band kernel when its preconditions hold (returns false otherwise: the caller uses the per-pixel kernel).
 // the hook is taken -- and forgotten -- at the TOP of the entry point it applies to, whatever becomes of the call (an empty batch, a
 // rejected argument): left armed it would pick the kernel of some later, unrelated call of the thread (round-4 advisor finding)
 static int take_pyramid_variant() {
@@ -819,6 +827,7 @@ static int take_pyramid_variant() {
   return v;
 }
 
+// Launches the band kernel when its preconditions hold (returns false otherwise: the caller uses the per-pixel kernel).
 template <bool PAIR>
 static bool launch_pyramid_band(const PyramidArgs& A, int images, hipStream_t st, const int variant) {
   const int H = A.H, W = A.W;
@@ -843,6 +852,51 @@ static bool launch_pyramid_band(const PyramidArgs& A, int images, hipStream_t st
   return true;
 }
 
+// What the three pyramid entry points check and fill in, in ONE place: the pointers (`ptrs`: those of the call itself), n_scales,
+// the shape (`group_ok`: the call's own count per sample; `images`: blockIdx.y's range), then per scale from `first` (1 planar: scale
+// 0 is the input itself; 0 pixel-interleaved) the output pointers, the size and the threads -- one per pixel, but FOUR pixels per
+// thread at scale 0 -- and the steps of the source coordinate.  y2: the second set of outputs of the pair form, else NULL.
+static int pyramid_setup(PyramidArgs& A, const char* who, bool ptrs, float* const* y, float* const* y2, int first, int N,
+                         bool group_ok, long long images, int H, int W, int n_scales) {
+  SFM_REQUIRE(ptrs, SFM_ERR_NULL, "%s: NULL pointer", who);
+  SFM_REQUIRE(n_scales >= 1 && n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "%s: n_scales=%d", who, n_scales);
+  SFM_REQUIRE(N >= 0 && group_ok && H >= 1 && W >= 1 && images <= 65535, SFM_ERR_SHAPE, "%s: bad shape", who);
+  A.H = H; A.W = W; A.n_scales = n_scales;
+  A.begin[0] = A.begin[first] = 0;
+  for (int s = first; s < n_scales; ++s) {
+    if (y2) SFM_REQUIRE(y[s] && y2[s], SFM_ERR_NULL, "%s: output of scale %d is NULL", who, s);
+    else SFM_REQUIRE(y[s], SFM_ERR_NULL, "%s: y[%d] is NULL", who, s);
+    A.y[s] = y[s];
+    if (y2) A.y2[s] = y2[s];
+    const int oH = A.oH[s] = H >> s, oW = A.oW[s] = W >> s;             // H // 2**s, base_model.py:70
+    SFM_REQUIRE(oH >= 1 && oW >= 1, SFM_ERR_SHAPE, "%s: scale %d is empty", who, s);
+    SFM_REQUIRE((long long)A.begin[s] + (long long)oH * oW < (1ll << 31), SFM_ERR_SHAPE, "%s: image too large", who);
+    A.begin[s + 1] = A.begin[s] + (s == 0 ? (oH * oW + 3) / 4 : oH * oW);
+    A.step_u[s] = oW > 1 ? (double)(W - 1) / (double)(oW - 1) : 0.0;
+    A.step_v[s] = oH > 1 ? (double)(H - 1) / (double)(oH - 1) : 0.0;
+    A.inv_oW[s] = 1.0f / (float)oW;
+  }
+  A.quads0 = A.begin[1];
+  return SFM_OK;
+}
+
+// The two pixel-interleaved forms: x (N,3G,H,W) -> y, and in the pair form x2 (N,3*G2,H,W) -> y2 in the same launch (G = 1 then).
+// `variant`: the hook, which the entry point has taken as its FIRST statement (see take_pyramid_variant).
+template <bool PAIR>
+static int pyramid_hwc_launch(const char* who, const int variant, const float* x, const float* x2, float* const* y, float* const* y2,
+                              int N, int G, int G2, int H, int W, int n_scales, void* stream) {
+  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
+  PyramidArgs A;
+  A.x = x; A.x2 = x2; A.n_first = N; A.G2 = G2;
+  const long long images = (long long)N * (G + G2);
+  if (int e = pyramid_setup(A, who, x && y && (!PAIR || (x2 && y2)), y, y2, 0, N, PAIR ? G2 >= 1 && G2 <= SFM_MAX_SRC : G >= 1, images, H, W,
+                            n_scales))
+    return e;
+  if (!launch_pyramid_band<PAIR>(A, (int)images, (hipStream_t)stream, variant))
+    hipLaunchKernelGGL(pyramid_hwc_fwd_kernel<PAIR>, dim3((A.begin[n_scales] + 255) / 256, (int)images), dim3(256), 0, (hipStream_t)stream, A);
+  return check_launch(who);
+}
+
 // ------------------------------------------------------------------------------------------
 // data_augmentation (datasets/kitti/kitti_raw_transformed.py:23-74) as one gather: random scaling
 // (F.resize_images to (int(H*ys), int(W*xs)), :32-45), random crop back to (H, W) at (oy, ox) (:48-59)
@@ -860,16 +914,9 @@ __global__ void augment_fwd_kernel(const float* __restrict__ x, const float* __r
   const bool flip = p[4] != 0.f;
   const int yo = j / W, xo = j - yo * W;
   const int Y = yo + oy, X = (flip ? (W - 1 - xo) : xo) + ox;          // position in the scaled image
-  const float u = W2 > 1 ? (float)((double)X * ((double)(W - 1) / (double)(W2 - 1))) : 0.f;
-  const float v = H2 > 1 ? (float)((double)Y * ((double)(H - 1) / (double)(H2 - 1))) : 0.f;
-  const int u0 = min(max((int)floorf(u), 0), max(W - 2, 0)), v0 = min(max((int)floorf(v), 0), max(H - 2, 0));
-  const int u1 = min(u0 + 1, W - 1), v1 = min(v0 + 1, H - 1);
-  const float wu1 = u - (float)u0, wv1 = v - (float)v0;
-  const float wu0 = 1.0f - wu1, wv0 = 1.0f - wv1;
-  const float* img = x + (size_t)plane * H * W;
-  const float top = img[v0 * W + u0] * wu0 + img[v0 * W + u1] * wu1;
-  const float bot = img[v1 * W + u0] * wu0 + img[v1 * W + u1] * wu1;
-  y[(size_t)plane * H * W + j] = top * wv0 + bot * wv1;
+  const float u = W2 > 1 ? resize_coord(X, (double)(W - 1) / (double)(W2 - 1)) : 0.f;
+  const float v = H2 > 1 ? resize_coord(Y, (double)(H - 1) / (double)(H2 - 1)) : 0.f;
+  y[(size_t)plane * H * W + j] = resize_read(resize_taps(u, v, H, W), x + (size_t)plane * H * W, W);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -889,10 +936,7 @@ template <bool BWD>
 __global__ void disp_act_kernel(const ActArgs A) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.begin[A.n_scales]) return;
-  int s = 0;
-#pragma unroll
-  for (int k = 1; k < SFM_MAX_SCALES; ++k)
-    if (k < A.n_scales && j >= A.begin[k]) s = k;
+  const int s = scale_of<0>(j, A.begin, A.n_scales);
   const long long jj = j - A.begin[s];
   if (!BWD) {
     const float x = A.a[s][jj];
@@ -1022,7 +1066,6 @@ int sfm_pose_proj_fwd(const float* pose6, const float* K, float* proj, int N, vo
   if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
   SFM_REQUIRE(pose6 && K && proj, SFM_ERR_NULL, "sfm_pose_proj_fwd: NULL pointer");
   SFM_REQUIRE(N >= 0, SFM_ERR_SHAPE, "sfm_pose_proj_fwd: N=%d", N);
-  if (N == 0) return SFM_OK;
   hipLaunchKernelGGL(pose_proj_fwd_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, pose6, K, proj, N);
   return check_launch("sfm_pose_proj_fwd");
 }
@@ -1031,7 +1074,6 @@ int sfm_pose_proj_bwd(const float* pose6, const float* K, const float* g_proj, f
   if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
   SFM_REQUIRE(pose6 && K && g_proj && d_pose6, SFM_ERR_NULL, "sfm_pose_proj_bwd: NULL pointer");
   SFM_REQUIRE(N >= 0, SFM_ERR_SHAPE, "sfm_pose_proj_bwd: N=%d", N);
-  if (N == 0) return SFM_OK;
   hipLaunchKernelGGL(pose_proj_bwd_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, pose6, K, g_proj, d_pose6, N);
   return check_launch("sfm_pose_proj_bwd");
 }
@@ -1086,56 +1128,60 @@ static int check_sampler_shape(const char* who, int N, int C, int H, int W, int 
   return SFM_OK;
 }
 
-int sfm_sampler_fwd(const float* x, const float* grid, float* y, int N, int C, int H, int W, int oH, int oW, void* stream) {
+// sfm_sampler_fwd and sfm_sampler_interp_fwd: the same checks and grid, each its kernel
+static int sampler_fwd_launch(const char* who, void (*kernel)(const float*, const float*, float*, int, int, int, int), const float* x,
+                              const float* grid, float* y, int N, int C, int H, int W, int oH, int oW, void* stream) {
   if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
-  SFM_REQUIRE(x && grid && y, SFM_ERR_NULL, "sfm_sampler_fwd: NULL pointer");
-  if (int e = check_sampler_shape("sfm_sampler_fwd", N, C, H, W, oH, oW)) return e;
-  if (N == 0 || oH * oW == 0) return SFM_OK;
-  hipLaunchKernelGGL(sampler_fwd_kernel, dim3((oH * oW + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, x, grid, y, C, H, W,
-                     oH * oW);
-  return check_launch("sfm_sampler_fwd");
+  SFM_REQUIRE(x && grid && y, SFM_ERR_NULL, "%s: NULL pointer", who);
+  if (int e = check_sampler_shape(who, N, C, H, W, oH, oW)) return e;
+  if (oH * oW == 0) return SFM_OK;
+  hipLaunchKernelGGL(kernel, dim3((oH * oW + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, x, grid, y, C, H, W, oH * oW);
+  return check_launch(who);
 }
 
-int sfm_sampler_bwd(const float* x, const float* grid, const float* gy, float* ggrid, float* gx, int N, int C, int H, int W,
-                    int oH, int oW, void* stream) {
-  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
-  SFM_REQUIRE(x && grid && gy && ggrid, SFM_ERR_NULL, "sfm_sampler_bwd: NULL pointer");
-  if (int e = check_sampler_shape("sfm_sampler_bwd", N, C, H, W, oH, oW)) return e;
-  if (N == 0 || oH * oW == 0) return SFM_OK;
-  const int row_blocks = (oH + 4 * SAMPLER_BWD_ROWS - 1) / (4 * SAMPLER_BWD_ROWS);
-  SFM_REQUIRE(N <= 65535 && row_blocks <= 65535, SFM_ERR_SHAPE, "sfm_sampler_bwd: N=%d / oH=%d exceed the grid", N, oH);
-  const dim3 g((oW + 63) / 64, row_blocks, N);
-  if (C <= SAMPLER_BWD_MAXC)   // the carried shares of up to four channels live in registers
-    hipLaunchKernelGGL(sampler_bwd_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, x, grid, gy, ggrid, gx, C, H, W, oH, oW);
-  else
-    hipLaunchKernelGGL(sampler_bwd_kernel<false>, g, dim3(256), 0, (hipStream_t)stream, x, grid, gy, ggrid, gx, C, H, W, oH, oW);
-  return check_launch("sfm_sampler_bwd");
+int sfm_sampler_fwd(const float* x, const float* grid, float* y, int N, int C, int H, int W, int oH, int oW, void* stream) {
+  return sampler_fwd_launch("sfm_sampler_fwd", sampler_fwd_kernel, x, grid, y, N, C, H, W, oH, oW, stream);
 }
 
 int sfm_sampler_interp_fwd(const float* x, const float* grid, float* y, int N, int C, int H, int W, int oH, int oW,
                            void* stream) {
+  return sampler_fwd_launch("sfm_sampler_interp_fwd", interp_fwd_kernel, x, grid, y, N, C, H, W, oH, oW, stream);
+}
+
+// sfm_sampler_bwd and sfm_sampler_interp_bwd: the same checks; the interp form zero-fills gx and scatters nothing
+static int sampler_bwd_launch(const char* who, bool interp, const float* x, const float* grid, const float* gy, float* ggrid,
+                              float* gx, int N, int C, int H, int W, int oH, int oW, void* stream) {
   if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
-  SFM_REQUIRE(x && grid && y, SFM_ERR_NULL, "sfm_sampler_interp_fwd: NULL pointer");
-  if (int e = check_sampler_shape("sfm_sampler_interp_fwd", N, C, H, W, oH, oW)) return e;
-  if (N == 0 || oH * oW == 0) return SFM_OK;
-  hipLaunchKernelGGL(interp_fwd_kernel, dim3((oH * oW + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, x, grid, y, C, H, W,
-                     oH * oW);
-  return check_launch("sfm_sampler_interp_fwd");
+  SFM_REQUIRE(x && grid && gy && ggrid, SFM_ERR_NULL, "%s: NULL pointer", who);
+  if (int e = check_sampler_shape(who, N, C, H, W, oH, oW)) return e;
+  const hipStream_t st = (hipStream_t)stream;
+  if (interp && gx) {  // spational_transformer_sampler_interp.py:148: gx = zeros_like(x), whatever the size of the output
+    hipError_t e = hipMemsetAsync(gx, 0, (size_t)N * C * H * W * sizeof(float), st);
+    if (e != hipSuccess) return fail((int)e, "%s: memset: %s", who, hipGetErrorString(e));
+  }
+  if (oH * oW == 0) return SFM_OK;
+  if (interp) {
+    hipLaunchKernelGGL(interp_bwd_kernel, dim3((oH * oW + 255) / 256, N), dim3(256), 0, st, x, grid, gy, ggrid, C, H, W, oH * oW);
+    return check_launch(who);
+  }
+  const int row_blocks = (oH + 4 * SAMPLER_BWD_ROWS - 1) / (4 * SAMPLER_BWD_ROWS);
+  SFM_REQUIRE(row_blocks <= 65535, SFM_ERR_SHAPE, "%s: N=%d / oH=%d exceed the grid", who, N, oH);
+  const dim3 g((oW + 63) / 64, row_blocks, N);
+  if (C <= SAMPLER_BWD_MAXC)   // the carried shares of up to four channels live in registers
+    hipLaunchKernelGGL(sampler_bwd_kernel<true>, g, dim3(256), 0, st, x, grid, gy, ggrid, gx, C, H, W, oH, oW);
+  else
+    hipLaunchKernelGGL(sampler_bwd_kernel<false>, g, dim3(256), 0, st, x, grid, gy, ggrid, gx, C, H, W, oH, oW);
+  return check_launch(who);
+}
+
+int sfm_sampler_bwd(const float* x, const float* grid, const float* gy, float* ggrid, float* gx, int N, int C, int H, int W,
+                    int oH, int oW, void* stream) {
+  return sampler_bwd_launch("sfm_sampler_bwd", false, x, grid, gy, ggrid, gx, N, C, H, W, oH, oW, stream);
 }
 
 int sfm_sampler_interp_bwd(const float* x, const float* grid, const float* gy, float* ggrid, float* gx, int N, int C, int H,
                            int W, int oH, int oW, void* stream) {
-  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
-  SFM_REQUIRE(x && grid && gy && ggrid, SFM_ERR_NULL, "sfm_sampler_interp_bwd: NULL pointer");
-  if (int e = check_sampler_shape("sfm_sampler_interp_bwd", N, C, H, W, oH, oW)) return e;
-  if (gx) {  // spational_transformer_sampler_interp.py:148: gx = zeros_like(x)
-    hipError_t e = hipMemsetAsync(gx, 0, (size_t)N * C * H * W * sizeof(float), (hipStream_t)stream);
-    if (e != hipSuccess) return fail((int)e, "sfm_sampler_interp_bwd: memset: %s", hipGetErrorString(e));
-  }
-  if (N == 0 || oH * oW == 0) return SFM_OK;
-  hipLaunchKernelGGL(interp_bwd_kernel, dim3((oH * oW + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, x, grid, gy, ggrid, C,
-                     H, W, oH * oW);
-  return check_launch("sfm_sampler_interp_bwd");
+  return sampler_bwd_launch("sfm_sampler_interp_bwd", true, x, grid, gy, ggrid, gx, N, C, H, W, oH, oW, stream);
 }
 
 int sfm_pyramid_variant(int variant) {
@@ -1146,82 +1192,23 @@ int sfm_pyramid_variant(int variant) {
 
 int sfm_pyramid_fwd(const float* x, float* const* y, int N, int C, int H, int W, int n_scales, void* stream) {
   if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
-  SFM_REQUIRE(x && y, SFM_ERR_NULL, "sfm_pyramid_fwd: NULL pointer");
-  SFM_REQUIRE(n_scales >= 1 && n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "sfm_pyramid_fwd: n_scales=%d", n_scales);
-  SFM_REQUIRE(N >= 0 && C >= 1 && H >= 1 && W >= 1 && (long long)N * C <= 65535, SFM_ERR_SHAPE, "sfm_pyramid_fwd: bad shape");
-  if (n_scales == 1) return SFM_OK;
   PyramidArgs A;
-  A.x = x; A.H = H; A.W = W; A.n_scales = n_scales;
-  A.begin[0] = A.begin[1] = 0;
-  for (int s = 1; s < n_scales; ++s) {
-    SFM_REQUIRE(y[s], SFM_ERR_NULL, "sfm_pyramid_fwd: y[%d] is NULL", s);
-    A.y[s] = y[s];
-    A.oH[s] = H >> s;                                                   // H // 2**s, base_model.py:70
-    A.oW[s] = W >> s;
-    SFM_REQUIRE(A.oH[s] >= 1 && A.oW[s] >= 1, SFM_ERR_SHAPE, "sfm_pyramid_fwd: scale %d is empty", s);
-    A.begin[s + 1] = A.begin[s] + A.oH[s] * A.oW[s];
-  }
-  pyramid_steps(A);
-  const int total = A.begin[n_scales];
-  hipLaunchKernelGGL(pyramid_fwd_kernel, dim3((total + 255) / 256, N * C), dim3(256), 0, (hipStream_t)stream, A);
+  A.x = x;
+  if (int e = pyramid_setup(A, "sfm_pyramid_fwd", x && y, y, nullptr, 1, N, C >= 1, (long long)N * C, H, W, n_scales)) return e;
+  if (n_scales == 1) return SFM_OK;
+  hipLaunchKernelGGL(pyramid_fwd_kernel, dim3((A.begin[n_scales] + 255) / 256, N * C), dim3(256), 0, (hipStream_t)stream, A);
   return check_launch("sfm_pyramid_fwd");
 }
 
 int sfm_pyramid_hwc_fwd(const float* x, float* const* y, int N, int G, int H, int W, int n_scales, void* stream) {
   const int variant = sfm::take_pyramid_variant();
-  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
-  SFM_REQUIRE(x && y, SFM_ERR_NULL, "sfm_pyramid_hwc_fwd: NULL pointer");
-  SFM_REQUIRE(n_scales >= 1 && n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "sfm_pyramid_hwc_fwd: n_scales=%d", n_scales);
-  SFM_REQUIRE(N >= 0 && G >= 1 && H >= 1 && W >= 1 && (long long)N * G <= 65535, SFM_ERR_SHAPE, "sfm_pyramid_hwc_fwd: bad shape");
-  PyramidArgs A;
-  A.x = x; A.H = H; A.W = W; A.n_scales = n_scales;
-  A.begin[0] = 0;
-  for (int s = 0; s < n_scales; ++s) {
-    SFM_REQUIRE(y[s], SFM_ERR_NULL, "sfm_pyramid_hwc_fwd: y[%d] is NULL", s);
-    A.y[s] = y[s];
-    A.oH[s] = H >> s;                                                   // H // 2**s, base_model.py:70
-    A.oW[s] = W >> s;
-    SFM_REQUIRE(A.oH[s] >= 1 && A.oW[s] >= 1, SFM_ERR_SHAPE, "sfm_pyramid_hwc_fwd: scale %d is empty", s);
-    SFM_REQUIRE((long long)A.begin[s] + (long long)A.oH[s] * A.oW[s] < (1ll << 31), SFM_ERR_SHAPE, "sfm_pyramid_hwc_fwd: image too large");
-    // threads: scale 0 four pixels each, the other scales one pixel each
-    A.begin[s + 1] = A.begin[s] + (s == 0 ? (A.oH[0] * A.oW[0] + 3) / 4 : A.oH[s] * A.oW[s]);
-  }
-  A.quads0 = A.begin[1];
-  pyramid_steps(A);
-  const int total = A.begin[n_scales];
-  if (!launch_pyramid_band<false>(A, N * G, (hipStream_t)stream, variant))
-    hipLaunchKernelGGL(pyramid_hwc_fwd_kernel<false>, dim3((total + 255) / 256, N * G), dim3(256), 0, (hipStream_t)stream, A);
-  return check_launch("sfm_pyramid_hwc_fwd");
+  return pyramid_hwc_launch<false>("sfm_pyramid_hwc_fwd", variant, x, nullptr, y, nullptr, N, G, 0, H, W, n_scales, stream);
 }
 
 int sfm_pyramid_pair_hwc_fwd(const float* tgt, const float* src, float* const* y_tgt, float* const* y_src, int N, int n_src, int H,
                              int W, int n_scales, void* stream) {
   const int variant = sfm::take_pyramid_variant();
-  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
-  SFM_REQUIRE(tgt && src && y_tgt && y_src, SFM_ERR_NULL, "sfm_pyramid_pair_hwc_fwd: NULL pointer");
-  SFM_REQUIRE(n_scales >= 1 && n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "sfm_pyramid_pair_hwc_fwd: n_scales=%d", n_scales);
-  SFM_REQUIRE(N >= 0 && n_src >= 1 && n_src <= SFM_MAX_SRC && H >= 1 && W >= 1 && (long long)N * (1 + n_src) <= 65535, SFM_ERR_SHAPE,
-              "sfm_pyramid_pair_hwc_fwd: bad shape");
-  PyramidArgs A;
-  A.x = tgt; A.x2 = src; A.n_first = N; A.G2 = n_src; A.H = H; A.W = W; A.n_scales = n_scales;
-  A.begin[0] = 0;
-  for (int s = 0; s < n_scales; ++s) {
-    SFM_REQUIRE(y_tgt[s] && y_src[s], SFM_ERR_NULL, "sfm_pyramid_pair_hwc_fwd: output of scale %d is NULL", s);
-    A.y[s] = y_tgt[s];
-    A.y2[s] = y_src[s];
-    A.oH[s] = H >> s;                                                   // H // 2**s, base_model.py:70
-    A.oW[s] = W >> s;
-    SFM_REQUIRE(A.oH[s] >= 1 && A.oW[s] >= 1, SFM_ERR_SHAPE, "sfm_pyramid_pair_hwc_fwd: scale %d is empty", s);
-    SFM_REQUIRE((long long)A.begin[s] + (long long)A.oH[s] * A.oW[s] < (1ll << 31), SFM_ERR_SHAPE, "sfm_pyramid_pair_hwc_fwd: image too large");
-    // threads: scale 0 four pixels each, the other scales one pixel each
-    A.begin[s + 1] = A.begin[s] + (s == 0 ? (A.oH[0] * A.oW[0] + 3) / 4 : A.oH[s] * A.oW[s]);
-  }
-  A.quads0 = A.begin[1];
-  pyramid_steps(A);
-  const int total = A.begin[n_scales];
-  if (!launch_pyramid_band<true>(A, N * (1 + n_src), (hipStream_t)stream, variant))
-    hipLaunchKernelGGL(pyramid_hwc_fwd_kernel<true>, dim3((total + 255) / 256, N * (1 + n_src)), dim3(256), 0, (hipStream_t)stream, A);
-  return check_launch("sfm_pyramid_pair_hwc_fwd");
+  return pyramid_hwc_launch<true>("sfm_pyramid_pair_hwc_fwd", variant, tgt, src, y_tgt, y_src, N, 1, n_src, H, W, n_scales, stream);
 }
 
 int sfm_augment_fwd(const float* imgs, const float* params, float* out, int B, int F, int C, int H, int W, void* stream) {
@@ -1248,7 +1235,6 @@ int sfm_resize_fwd(const float* x, float* y, int N, int C, int H, int W, int oH,
   SFM_REQUIRE(x && y, SFM_ERR_NULL, "sfm_resize_fwd: NULL pointer");
   SFM_REQUIRE(N >= 0 && C >= 1 && H >= 1 && W >= 1 && oH >= 1 && oW >= 1, SFM_ERR_SHAPE, "sfm_resize_fwd: bad shape");
   SFM_REQUIRE((long long)N * C <= 65535, SFM_ERR_SHAPE, "sfm_resize_fwd: N*C=%lld > 65535", (long long)N * C);
-  if (N == 0) return SFM_OK;
   hipLaunchKernelGGL(resize_fwd_kernel, dim3((oH * oW + 255) / 256, N * C), dim3(256), 0, (hipStream_t)stream, x, y, H, W, oH, oW);
   return check_launch("sfm_resize_fwd");
 }
