@@ -25,6 +25,24 @@ SMOOTH_NONE, SMOOTH_SECOND_ORDER, SMOOTH_EDGE_AWARE = 0, 1, 2
 SMOOTH_MODES = {None: SMOOTH_NONE, "none": SMOOTH_NONE, "second_order": SMOOTH_SECOND_ORDER,
                 "edge_aware": SMOOTH_EDGE_AWARE}
 
+
+
+def _setting(table, what, name):
+    if name not in table:
+        raise ValueError("%s must be one of %s" % (what, sorted(k for k in table if k)))
+    return table[name]
+
+
+def smooth_mode_id(name):
+    """SMOOTH_* of a `smooth_mode` argument; anything outside the table is a ValueError"""
+    return _setting(SMOOTH_MODES, "smooth_mode", name)
+
+
+def projection_id(name):
+    """SFM_PROJECTION_* of a `projection` argument; anything outside the table is a ValueError"""
+    return _setting(PROJECTIONS, "projection", name)
+
+
 ERR_NULL, ERR_SHAPE, ERR_CONFIG, ERR_WORKSPACE = -1, -2, -3, -4
 
 _FP = C.c_void_p   # device float*

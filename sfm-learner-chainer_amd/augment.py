@@ -9,13 +9,11 @@ the same parameters; the image work (resize + crop + flip of every frame) is one
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib
+from ._lib import lib
 
 __all__ = ["sample_params", "augment_intrinsics", "augment_images", "data_augmentation", "get_multi_scale_intrinsics"]
 
@@ -72,9 +70,7 @@ def augment_images(imgs, params):
     B, F, Cc, H, W = imgs.shape
     p = torch.from_numpy(np.ascontiguousarray(np.asarray(params)[:, 2:7], dtype=np.float32)).to(imgs.device)
     out = torch.empty_like(imgs)
-    with torch.cuda.device(imgs.device):
-        check(lib.sfm_augment_fwd(C.c_void_p(imgs.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(out.data_ptr()),
-                                  B, F, Cc, H, W, ops._stream()))
+    ops._launch(imgs.device, lib.sfm_augment_fwd, ops._p(imgs), ops._p(p), ops._p(out), B, F, Cc, H, W)
     return out
 
 

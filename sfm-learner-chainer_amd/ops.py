@@ -14,23 +14,43 @@ from ._lib import SfmLossDesc, check, lib
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "warp_fwd", "warp_bwd", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss"]
 
+FLOAT32 = (torch.float32,)
+FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
+_DTYPE_NAMES = {FLOAT32: "float32 (dtype.char == 'f')", FLOATS: "float32, bfloat16 or float16"}
 
-def _dev(t, name, ndim=None):
-    """float32 CUDA(ROCm) tensor, contiguous; anything else is a type error, as in the
+
+def _dev(t, name, ndim=None, dtypes=FLOAT32):
+    """A CUDA(ROCm) tensor of one of `dtypes`, made contiguous; anything else is a type error, as in the
     reference's check_type_forward (spational_transformer_sampler_interp.py:11-24)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s: expected a torch.Tensor on a ROCm device, got %s" % (name, type(t).__name__))
     if not t.is_cuda:
         raise TypeError("%s: CPU arrays are not supported by this build (GPU-only, no CPU fallback)" % name)
-    if t.dtype != torch.float32:
-        raise TypeError("%s: expected dtype float32 (dtype.char == 'f'), got %s" % (name, t.dtype))
+    if t.dtype not in dtypes:
+        raise TypeError("%s: expected dtype %s, got %s" % (name, _DTYPE_NAMES[dtypes], t.dtype))
     if ndim is not None and t.dim() != ndim:
         raise TypeError("%s: expected ndim == %d, got %d" % (name, ndim, t.dim()))
     return t.contiguous()
 
 
+def _devs(ts, name, ndim=None):
+    return [_dev(t, "%s[%d]" % (name, k), ndim) for k, t in enumerate(ts)]
+
+
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ptr_array(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _numel_array(ts):
+    return (C.c_longlong * len(ts))(*[t.numel() for t in ts])
+
+
+def _empty(shapes, device):
+    return [torch.empty(shape, dtype=torch.float32, device=device) for shape in shapes]
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -44,14 +64,25 @@ def _stream(index=None):
     return C.c_void_p(torch.cuda.current_stream(index).cuda_stream)
 
 
+def _launch(device, fn, *args):
+    """THE call through the C ABI: fn(*args, stream) on the stream torch currently issues work on for `device`, return code
+    checked.  The device guard is entered only when `device` is not the current one (a fused step is 15-70 us of GPU time and
+    its host side about 7 us: the guard alone, let alone a generator-based context manager, would show)."""
+    idx = device.index
+    if torch.cuda.current_device() == idx:
+        check(fn(*args, _stream(idx)))
+    else:
+        with torch.cuda.device(idx):
+            check(fn(*args, _stream(idx)))
+
+
 def pose_proj_fwd(pose6, K):
     pose6, K = _dev(pose6, "pose6", 2), _dev(K, "K", 3)
     N = pose6.shape[0]
     if pose6.shape[1] != 6 or tuple(K.shape) != (N, 3, 3):
         raise TypeError("pose6 must be (N,6) and K (N,3,3)")
     out = torch.empty((N, 4, 4), dtype=torch.float32, device=pose6.device)
-    with torch.cuda.device(pose6.device):
-        check(lib.sfm_pose_proj_fwd(_p(pose6), _p(K), _p(out), N, _stream()))
+    _launch(pose6.device, lib.sfm_pose_proj_fwd, _p(pose6), _p(K), _p(out), N)
     return out
 
 
@@ -59,8 +90,7 @@ def pose_proj_bwd(pose6, K, g_proj):
     pose6, K, g_proj = _dev(pose6, "pose6", 2), _dev(K, "K", 3), _dev(g_proj, "g_proj", 3)
     N = pose6.shape[0]
     out = torch.empty((N, 6), dtype=torch.float32, device=pose6.device)
-    with torch.cuda.device(pose6.device):
-        check(lib.sfm_pose_proj_bwd(_p(pose6), _p(K), _p(g_proj), _p(out), N, _stream()))
+    _launch(pose6.device, lib.sfm_pose_proj_bwd, _p(pose6), _p(K), _p(g_proj), _p(out), N)
     return out
 
 
@@ -85,8 +115,7 @@ def warp_fwd(imgs, depth, pose6, K):
     row of its broadcast (models/base_model.py:82-84)."""
     imgs, depth, drows, pose6, K, N, Cc, H, W = _warp_args(imgs, depth, pose6, K)
     out = torch.empty_like(imgs)
-    with torch.cuda.device(imgs.device):
-        check(lib.sfm_warp_fwd(_p(imgs), _p(depth), drows, _p(pose6), _p(K), _p(out), N, Cc, H, W, _stream()))
+    _launch(imgs.device, lib.sfm_warp_fwd, _p(imgs), _p(depth), drows, _p(pose6), _p(K), _p(out), N, Cc, H, W)
     return out
 
 
@@ -100,9 +129,8 @@ def warp_bwd(imgs, depth, pose6, K, g_warped, want_d_src=False):
     d_src = torch.zeros_like(imgs) if want_d_src else None
     nbytes = lib.sfm_warp_bwd_workspace_bytes(N, H, W)
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=imgs.device)
-    with torch.cuda.device(imgs.device):
-        check(lib.sfm_warp_bwd(_p(imgs), _p(depth), drows, _p(pose6), _p(K), _p(g_warped), _p(d_depth), _p(d_pose),
-                               _p(d_src), _p(ws), nbytes, N, Cc, H, W, _stream()))
+    _launch(imgs.device, lib.sfm_warp_bwd, _p(imgs), _p(depth), drows, _p(pose6), _p(K), _p(g_warped), _p(d_depth), _p(d_pose),
+            _p(d_src), _p(ws), nbytes, N, Cc, H, W)
     return d_depth, d_pose, d_src
 
 
@@ -119,8 +147,7 @@ def _sampler_args(x, grid):
 def _sampler(fwd, x, grid):
     x, grid, N, Cc, H, W, oH, oW = _sampler_args(x, grid)
     y = torch.empty((N, Cc, oH, oW), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(fwd(_p(x), _p(grid), _p(y), N, Cc, H, W, oH, oW, _stream()))
+    _launch(x.device, fwd, _p(x), _p(grid), _p(y), N, Cc, H, W, oH, oW)
     return y
 
 
@@ -131,8 +158,7 @@ def _sampler_b(bwd, x, grid, gy, want_gx):
         raise TypeError("gy must be (N,C,oH,oW)")
     ggrid = torch.empty_like(grid)
     gx = torch.zeros_like(x) if want_gx else None
-    with torch.cuda.device(x.device):
-        check(bwd(_p(x), _p(grid), _p(gy), _p(ggrid), _p(gx), N, Cc, H, W, oH, oW, _stream()))
+    _launch(x.device, bwd, _p(x), _p(grid), _p(gy), _p(ggrid), _p(gx), N, Cc, H, W, oH, oW)
     return gx, ggrid
 
 
@@ -157,9 +183,15 @@ def resize(x, out_hw):
     N, Cc, H, W = x.shape
     oH, oW = int(out_hw[0]), int(out_hw[1])
     y = torch.empty((N, Cc, oH, oW), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib.sfm_resize_fwd(_p(x), _p(y), N, Cc, H, W, oH, oW, _stream()))
+    _launch(x.device, lib.sfm_resize_fwd, _p(x), _p(y), N, Cc, H, W, oH, oW)
     return y
+
+
+def _pyramid_shapes(n_scales, N, G, H, W, tail=()):
+    """The shape of every level of a pyramid of `n_scales` scales; a scale count the library does not take is a type error."""
+    if not 1 <= n_scales <= _lib.SFM_MAX_SCALES:
+        raise TypeError("n_scales must be in [1, %d]" % _lib.SFM_MAX_SCALES)
+    return [(N, G, H >> s, W >> s) + tail for s in range(n_scales)]
 
 
 def pyramid(x, n_scales, out=None):
@@ -168,17 +200,14 @@ def pyramid(x, n_scales, out=None):
     (a caller that needs scale 0 at a fixed address copies it)."""
     x = _dev(x, "x", 4)
     N, Cc, H, W = x.shape
-    if not 1 <= n_scales <= _lib.SFM_MAX_SCALES:
-        raise TypeError("n_scales must be in [1, %d]" % _lib.SFM_MAX_SCALES)
-    if out is not None:
-        if len(out) != n_scales or any(tuple(out[s].shape) != (N, Cc, H >> s, W >> s) for s in range(n_scales)):
-            raise TypeError("pyramid: `out` does not match the input")
-        outs = [x] + list(out[1:])
+    shapes = _pyramid_shapes(n_scales, N, Cc, H, W)
+    if out is None:
+        outs = [x] + _empty(shapes[1:], x.device)
+    elif [tuple(t.shape) for t in out] != shapes:
+        raise TypeError("pyramid: `out` does not match the input")
     else:
-        outs = [x] + [torch.empty((N, Cc, H >> s, W >> s), dtype=torch.float32, device=x.device) for s in range(1, n_scales)]
-    ptrs = (C.c_void_p * n_scales)(*[t.data_ptr() for t in outs])
-    with torch.cuda.device(x.device):
-        check(lib.sfm_pyramid_fwd(_p(x), ptrs, N, Cc, H, W, n_scales, _stream()))
+        outs = [x] + list(out[1:])
+    _launch(x.device, lib.sfm_pyramid_fwd, _p(x), _ptr_array(outs), N, Cc, H, W, n_scales)
     return outs
 
 
@@ -189,13 +218,8 @@ def pyramid_hwc(x, n_scales):
     N, Cc, H, W = x.shape
     if Cc % 3 != 0:
         raise TypeError("pyramid_hwc: the channel count must be a multiple of 3 (RGB images), got %d" % Cc)
-    if not 1 <= n_scales <= _lib.SFM_MAX_SCALES:
-        raise TypeError("n_scales must be in [1, %d]" % _lib.SFM_MAX_SCALES)
-    G = Cc // 3
-    outs = [torch.empty((N, G, H >> s, W >> s, 3), dtype=torch.float32, device=x.device) for s in range(n_scales)]
-    ptrs = (C.c_void_p * n_scales)(*[t.data_ptr() for t in outs])
-    with torch.cuda.device(x.device):
-        check(lib.sfm_pyramid_hwc_fwd(_p(x), ptrs, N, G, H, W, n_scales, _stream()))
+    outs = _empty(_pyramid_shapes(n_scales, N, Cc // 3, H, W, (3,)), x.device)
+    _launch(x.device, lib.sfm_pyramid_hwc_fwd, _p(x), _ptr_array(outs), N, Cc // 3, H, W, n_scales)
     return outs
 
 
@@ -208,45 +232,35 @@ def pyramid_pair_hwc(tgt, src, n_scales, out=None, per_pixel=False):
     N, Ct, H, W = tgt.shape
     if Ct != 3 or src.shape[0] != N or tuple(src.shape[2:]) != (H, W) or src.shape[1] % 3 != 0 or src.shape[1] == 0:
         raise TypeError("pyramid_pair_hwc: expected tgt (N,3,H,W) and src (N,3*n_src,H,W), got %s and %s" % (tuple(tgt.shape), tuple(src.shape)))
-    if not 1 <= n_scales <= _lib.SFM_MAX_SCALES:
-        raise TypeError("n_scales must be in [1, %d]" % _lib.SFM_MAX_SCALES)
     n_src = src.shape[1] // 3
-    if out is not None:
+    t_shapes, s_shapes = _pyramid_shapes(n_scales, N, 1, H, W, (3,)), _pyramid_shapes(n_scales, N, n_src, H, W, (3,))
+    given = out is not None
+    if given:
         yt, ys = out
-        if len(yt) != n_scales or len(ys) != n_scales or tuple(yt[0].shape) != (N, 1, H, W, 3) or tuple(ys[0].shape) != (N, n_src, H, W, 3):
+        if len(yt) != n_scales or len(ys) != n_scales or tuple(yt[0].shape) != t_shapes[0] or tuple(ys[0].shape) != s_shapes[0]:
             raise TypeError("pyramid_pair_hwc: `out` does not match the inputs")
         if yt[0].device != tgt.device or ys[0].device != tgt.device:
             raise TypeError("pyramid_pair_hwc: `out` lives on %s, the inputs on %s" % (yt[0].device, tgt.device))
-        # (the pointer arrays of the buffers are built once -- a step is 15-60 us -- and are only reused while `out` still holds the
-        #  very arrays they were built from: round-5 advisor finding, a caller that swapped an element used to be written through a
-        #  stale pointer)
-        key = tuple(t.data_ptr() for t in yt) + tuple(t.data_ptr() for t in ys)
-        cached = getattr(out, "_ptrs", None)
-        ptrs = cached[1] if cached is not None and cached[0] == key else None
-        if ptrs is None:
+    else:
+        yt, ys = tuple(_empty(t_shapes, tgt.device)), tuple(_empty(s_shapes, tgt.device))
+        out = _PyramidPair((yt, ys))
+    # (the pointer arrays of the buffers are built once -- a step is 15-60 us -- and are only reused while `out` still holds the
+    #  very arrays they were built from: round-5 advisor finding, a caller that swapped an element used to be written through a
+    #  stale pointer)
+    key = tuple(t.data_ptr() for t in yt) + tuple(t.data_ptr() for t in ys)
+    cached = getattr(out, "_ptrs", None)
+    if cached is None or cached[0] != key:
+        if given:
             for s in range(n_scales):
-                if tuple(yt[s].shape) != (N, 1, H >> s, W >> s, 3) or tuple(ys[s].shape) != (N, n_src, H >> s, W >> s, 3) or \
-                        not yt[s].is_contiguous() or not ys[s].is_contiguous() or yt[s].dtype != torch.float32 or ys[s].dtype != torch.float32 or \
-                        yt[s].device != tgt.device or ys[s].device != tgt.device:
-                    raise TypeError("pyramid_pair_hwc: `out` scale %d does not match the inputs" % s)
-    else:
-        yt = tuple(torch.empty((N, 1, H >> s, W >> s, 3), dtype=torch.float32, device=tgt.device) for s in range(n_scales))
-        ys = tuple(torch.empty((N, n_src, H >> s, W >> s, 3), dtype=torch.float32, device=tgt.device) for s in range(n_scales))
-        out, ptrs = _PyramidPair((yt, ys)), None
-    if ptrs is None:
-        ptrs = (_ptr_array(yt), _ptr_array(ys))
+                for t, shape in ((yt[s], t_shapes[s]), (ys[s], s_shapes[s])):
+                    if tuple(t.shape) != shape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != tgt.device:
+                        raise TypeError("pyramid_pair_hwc: `out` scale %d does not match the inputs" % s)
+        cached = (key, (_ptr_array(yt), _ptr_array(ys)))
         if isinstance(out, _PyramidPair):
-            out._ptrs = (tuple(t.data_ptr() for t in yt) + tuple(t.data_ptr() for t in ys), ptrs)
-    idx = tgt.device.index
-    if torch.cuda.current_device() == idx:
-        if per_pixel:
-            check(lib.sfm_pyramid_variant(1))
-        check(lib.sfm_pyramid_pair_hwc_fwd(_p(tgt), _p(src), ptrs[0], ptrs[1], N, n_src, H, W, n_scales, _stream(idx)))
-    else:
-        with torch.cuda.device(tgt.device):
-            if per_pixel:
-                check(lib.sfm_pyramid_variant(1))
-            check(lib.sfm_pyramid_pair_hwc_fwd(_p(tgt), _p(src), ptrs[0], ptrs[1], N, n_src, H, W, n_scales, _stream(idx)))
+            out._ptrs = cached
+    if per_pixel:
+        check(lib.sfm_pyramid_variant(1))
+    _launch(tgt.device, lib.sfm_pyramid_pair_hwc_fwd, _p(tgt), _p(src), *cached[1], N, n_src, H, W, n_scales)
     return out
 
 
@@ -261,30 +275,115 @@ def to_hwc(x):
     return x.reshape(N, Cc // 3, 3, h, w).permute(0, 1, 3, 4, 2).contiguous()
 
 
-def _ptr_array(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 def disp_act_fwd(xs):
     """[10 * sigmoid(x) + 0.01 for x in xs] in one launch (models/disp_net.py:104-122)."""
-    xs = [_dev(x, "xs[%d]" % k) for k, x in enumerate(xs)]
+    xs = _devs(xs, "xs")
     outs = [torch.empty_like(x) for x in xs]
-    n = (C.c_longlong * len(xs))(*[x.numel() for x in xs])
-    with torch.cuda.device(xs[0].device):
-        check(lib.sfm_disp_act_fwd(_ptr_array(xs), _ptr_array(outs), n, len(xs), _stream()))
+    _launch(xs[0].device, lib.sfm_disp_act_fwd, _ptr_array(xs), _ptr_array(outs), _numel_array(xs), len(xs))
     return outs
 
 
 def disp_act_bwd(disps, g_disps):
-    disps = [_dev(x, "disps[%d]" % k) for k, x in enumerate(disps)]
-    g_disps = [_dev(x, "g_disps[%d]" % k) for k, x in enumerate(g_disps)]
+    disps, g_disps = _devs(disps, "disps"), _devs(g_disps, "g_disps")
     if any(a.shape != b.shape for a, b in zip(disps, g_disps)):
         raise TypeError("g_disps must match disps")
     outs = [torch.empty_like(x) for x in disps]
-    n = (C.c_longlong * len(disps))(*[x.numel() for x in disps])
-    with torch.cuda.device(disps[0].device):
-        check(lib.sfm_disp_act_bwd(_ptr_array(disps), _ptr_array(g_disps), _ptr_array(outs), n, len(disps), _stream()))
+    _launch(disps[0].device, lib.sfm_disp_act_bwd, _ptr_array(disps), _ptr_array(g_disps), _ptr_array(outs), _numel_array(disps),
+            len(disps))
     return outs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the fused loss: descriptor, workspace, layout -- shared by FusedLoss.bind, torch_api._plan and links.SFMLearnerLoss
+# ---------------------------------------------------------------------------------------------------------------------------
+# SFM_LAYOUT_HWC forms the byte offset of a gather inside one image exactly in fp32 (include/sfmwarp.h): an image of a scale
+# must have fewer than 2^24 / 12 pixels there.  Larger frames take the reference's planar layout (same results).
+HWC_MAX_PIXELS = (1 << 24) // 12
+_LAYOUTS = {"planar": _lib.SFM_LAYOUT_PLANAR, "hwc": _lib.SFM_LAYOUT_HWC}
+
+
+def layout_for(H, W):
+    """The image layout ("hwc" or "planar") the link and the torch route pick for full-resolution frames of H x W."""
+    return "hwc" if H * W < HWC_MAX_PIXELS else "planar"
+
+
+def loss_desc(B, norm_B, n_src, hw, settings, layout):
+    """An SfmLossDesc with every non-pointer field set.  hw: (h, w) of each scale; settings: (smooth_reg, exp_reg, ssim_rate,
+    smooth_mode, projection), the last two as _lib.SMOOTH_* / _lib.SFM_PROJECTION_*; layout: "planar" or "hwc".  (Whether
+    there are explainability masks shows in the pointers alone.)"""
+    d = SfmLossDesc()
+    d.B, d.norm_B, d.n_src, d.n_scales = B, norm_B, n_src, len(hw)
+    d.smooth_reg, d.exp_reg, d.ssim_rate, d.smooth_mode, d.projection = settings
+    d.image_layout = _LAYOUTS[layout]
+    for s, (h, w) in enumerate(hw):
+        d.H[s], d.W[s] = h, w
+    return d
+
+
+def workspace_bytes(d):
+    """sfm_loss_workspace_bytes of a descriptor whose pointers are bound (any non-NULL value); 0 bytes means the library
+    refuses the descriptor: a ValueError with its message."""
+    nbytes = lib.sfm_loss_workspace_bytes(C.byref(d)) if d.B > 0 else 256
+    if nbytes == 0:
+        check(lib.sfm_loss_fwd(C.byref(d), None, None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid loss descriptor")
+    return nbytes
+
+
+def _point(field, arrays):
+    """field[k] = the address of arrays[k] (a pointer array of the descriptor); None leaves the entry as it is"""
+    for k, t in enumerate(arrays):
+        if t is not None:
+            field[k] = t.data_ptr()
+
+
+def _own(buffers, key, k, shape, device):
+    """The caller's array `buffers[key][k]` if it gave one, else a fresh one"""
+    if buffers.get(key) is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    t = buffers[key] if key == "loss5" else buffers[key][k]
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous() \
+            or tuple(t.shape) != tuple(shape):
+        raise TypeError("buffers[%r][%d]: expected a contiguous float32 array of shape %s on %s" % (key, k, tuple(shape), device))
+    return t
+
+
+def _owns(buffers, key, shapes, device):
+    return [_own(buffers, key, k, shape, device) for k, shape in enumerate(shapes)]
+
+
+def _d_src_arrays(buffers, want_d_src, shapes, device):
+    """(the one allocation behind them or None, [a d_src array or None per scale]).  want_d_src: True, or one flag per scale --
+    SfmLossDesc.d_src[s] may be NULL for any scale; buffers["d_srcs"], the caller's arrays, replaces it.  Always planar."""
+    given = buffers.get("d_srcs")
+    if given is not None:
+        return None, [_own(buffers, "d_srcs", s, shape, device) if given[s] is not None else None for s, shape in enumerate(shapes)]
+    want = [bool(want_d_src[s] if isinstance(want_d_src, (list, tuple)) else want_d_src) for s in range(len(shapes))]
+    if not any(want):
+        return None, [None] * len(shapes)
+    # the d_src arrays of all bound scales are views of ONE allocation: the library accumulates into them (float atomics), so every
+    # backward starts by clearing them -- one fill kernel instead of one per scale
+    numel = [shape[0] * shape[1] * shape[2] * shape[3] if on else 0 for shape, on in zip(shapes, want)]
+    whole = torch.zeros((sum(numel),), dtype=torch.float32, device=device)
+    return whole, [part.view(shape) if on else None for part, shape, on in zip(whole.split(numel), shapes, want)]
+
+
+def _place_workspace(ws, nbytes, device):
+    """(tensor, address, bytes) of the workspace as include/sfmwarp.h states it: sfm_loss_workspace_bytes bytes on a 256-byte
+    boundary, content undefined -- the caller's `ws`, all of it, or a fresh allocation (which starts on a 512-byte boundary;
+    should an allocator ever hand out less, 256 spare bytes absorb it)"""
+    if ws is not None:
+        if not isinstance(ws, torch.Tensor) or ws.device != device or not ws.is_contiguous():
+            raise TypeError("buffers['ws']: expected a contiguous tensor on %s" % (device,))
+        ptr, have = ws.data_ptr(), ws.numel() * ws.element_size()
+        if ptr % 256 or have < nbytes:
+            raise ValueError("buffers['ws']: need %d bytes on a 256-byte boundary, got %d bytes at offset %d mod 256"
+                             % (nbytes, have, ptr % 256))
+        return ws, ptr, have
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    if ws.data_ptr() % 256:
+        ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, nbytes
 
 
 class FusedLoss:
@@ -295,15 +394,11 @@ class FusedLoss:
     def __init__(self, smooth_reg=0.0, exp_reg=0.0, ssim_rate=0.0, smooth_mode="second_order", projection="fast"):
         """projection: "fast" (SFM_PROJECTION_FAST) or "reference_order" (SFM_PROJECTION_REFERENCE_ORDER: the per-pixel chain of
         models/transform.py:105-108,122-131 in the reference's own rounding sequence; include/sfmwarp.h says what each guarantees)."""
-        if smooth_mode not in _lib.SMOOTH_MODES:
-            raise ValueError("smooth_mode must be one of %s" % sorted(k for k in _lib.SMOOTH_MODES if k))
-        if projection not in _lib.PROJECTIONS:
-            raise ValueError("projection must be one of %s" % sorted(k for k in _lib.PROJECTIONS if k))
-        self.projection = _lib.PROJECTIONS[projection]
+        self.smooth_mode = _lib.smooth_mode_id(smooth_mode)
+        self.projection = _lib.projection_id(projection)
         self.smooth_reg = float(smooth_reg or 0.0)
         self.exp_reg = float(exp_reg or 0.0)
         self.ssim_rate = float(ssim_rate or 0.0)
-        self.smooth_mode = _lib.SMOOTH_MODES[smooth_mode]
         self.desc = None
         self._keep = None
 
@@ -318,7 +413,38 @@ class FusedLoss:
         arrays are cleared before every backward like the own ones), "loss5" ((5,) float32) and "ws" (a contiguous device tensor of
         any dtype that starts on a 256-byte boundary; ALL its bytes are handed over as the workspace, and it must hold at least
         sfm_loss_workspace_bytes).  Float arrays need the shapes given above and 4-byte alignment, nothing more."""
-        if layout not in ("planar", "hwc"):
+        keep = self._check_inputs(tgt_pyr, src_pyr, intrinsics, disps, poses, masks, layout)
+        tgt_pyr, src_pyr, intrinsics, disps, poses, masks = keep
+        B, n_src, dev = tgt_pyr[0].shape[0], len(poses), tgt_pyr[0].device
+        hw = [tuple(t.shape[2:]) for t in disps]
+        d = loss_desc(B, int(norm_B if norm_B is not None else B), n_src, hw,
+                      (self.smooth_reg, self.exp_reg, self.ssim_rate, self.smooth_mode, self.projection), layout)
+        # outputs: the caller's (`buffers`) or fresh ones
+        buffers = dict(buffers or {})
+        use_masks = self.exp_reg > 0
+        d_disps = _owns(buffers, "d_disps", [t.shape for t in disps], dev)
+        d_poses = _owns(buffers, "d_poses", [t.shape for t in poses], dev)
+        d_masks = _owns(buffers, "d_masks", [t.shape for t in masks], dev) if use_masks else None
+        warped = _owns(buffers, "warped", [(B, n_src, 3, h, w) for h, w in hw], dev) if want_warped else None     # always planar
+        d_src_all, d_srcs = _d_src_arrays(buffers, want_d_src, [(B, 3 * n_src, h, w) for h, w in hw], dev)
+        d.intrinsics = intrinsics.data_ptr()
+        for field, arrays in ((d.tgt, tgt_pyr), (d.src, src_pyr), (d.disp, disps), (d.pose, poses), (d.d_disp, d_disps),
+                              (d.d_pose, d_poses), (d.d_src, d_srcs), (d.mask_logits, masks if use_masks else ()),
+                              (d.d_mask, d_masks or ()), (d.warped, warped or ())):
+            _point(field, arrays)
+        self.ws, self._ws_ptr, self._ws_bytes = _place_workspace(buffers.get("ws"), workspace_bytes(d), dev)
+        self.loss5 = torch.zeros((5,), dtype=torch.float32, device=dev) if buffers.get("loss5") is None \
+            else _own(buffers, "loss5", 0, (5,), dev)
+        self.desc, self.device = d, dev
+        self._desc_ref, self._ws_arg, self._loss5_arg = C.byref(d), C.c_void_p(self._ws_ptr), _p(self.loss5)
+        self.d_disps, self.d_poses, self.d_masks, self.warped = d_disps, d_poses, d_masks, warped
+        self._d_src_all, self.d_srcs = d_src_all, (d_srcs if any(t is not None for t in d_srcs) else None)
+        self._keep = keep
+        return self
+
+    def _check_inputs(self, tgt_pyr, src_pyr, intrinsics, disps, poses, masks, layout):
+        """bind's arguments as contiguous float32 device arrays of consistent shapes, in the order of `_keep`"""
+        if layout not in _LAYOUTS:
             raise ValueError("layout must be 'planar' or 'hwc', got %r" % (layout,))
         hwc = layout == "hwc"
         S = len(disps)
@@ -326,116 +452,29 @@ class FusedLoss:
             raise TypeError("tgt_pyr, src_pyr and disps must have one entry per scale")
         if S > _lib.SFM_MAX_SCALES or len(poses) > _lib.SFM_MAX_SRC:
             raise TypeError("at most %d scales and %d sources" % (_lib.SFM_MAX_SCALES, _lib.SFM_MAX_SRC))
-        tgt_pyr = [_dev(t, "tgt_pyr[%d]" % s, 5 if hwc else 4) for s, t in enumerate(tgt_pyr)]
-        src_pyr = [_dev(t, "src_pyr[%d]" % s, 5 if hwc else 4) for s, t in enumerate(src_pyr)]
-        disps = [_dev(t, "disps[%d]" % s, 4) for s, t in enumerate(disps)]
-        poses = [_dev(t, "poses[%d]" % i, 2) for i, t in enumerate(poses)]
+        tgt_pyr, src_pyr = _devs(tgt_pyr, "tgt_pyr", 5 if hwc else 4), _devs(src_pyr, "src_pyr", 5 if hwc else 4)
+        disps, poses = _devs(disps, "disps", 4), _devs(poses, "poses", 2)
         intrinsics = _dev(intrinsics, "intrinsics", 4)
-        B = tgt_pyr[0].shape[0]
-        n_src = len(poses)
-        dev = tgt_pyr[0].device
+        B, n_src = tgt_pyr[0].shape[0], len(poses)
         if tuple(intrinsics.shape) != (B, S, 3, 3):
             raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(intrinsics.shape)))
-        use_masks = self.exp_reg > 0
+        use_masks = self.exp_reg > 0         # (without the term, `masks` is kept as given and never read)
         if use_masks:
             if masks is None:
                 raise ValueError("exp_reg > 0 needs the explainability logits (masks)")
-            masks = [_dev(t, "masks[%d]" % s, 4) for s, t in enumerate(masks)]
-        d = SfmLossDesc()
-        d.B, d.norm_B, d.n_src, d.n_scales = B, int(norm_B if norm_B is not None else B), n_src, S
-        d.smooth_reg, d.exp_reg, d.ssim_rate, d.smooth_mode = self.smooth_reg, self.exp_reg, self.ssim_rate, self.smooth_mode
-        d.intrinsics = intrinsics.data_ptr()
-        d.image_layout = _lib.SFM_LAYOUT_HWC if hwc else _lib.SFM_LAYOUT_PLANAR
-        d.projection = self.projection
-        d_disps, d_masks, d_srcs, warped = [], [], [], []
-        buffers = dict(buffers or {})
-
-        def own(key, k, shape):
-            """the caller's array `buffers[key][k]` if it gave one, else a fresh one"""
-            if buffers.get(key) is None:
-                return torch.empty(shape, dtype=torch.float32, device=dev)
-            t = buffers[key] if key == "loss5" else buffers[key][k]
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
-                    or tuple(t.shape) != tuple(shape):
-                raise TypeError("buffers[%r][%d]: expected a contiguous float32 array of shape %s on %s" % (key, k, tuple(shape), dev))
-            return t
-
-        given_src = buffers.get("d_srcs")
-        if given_src is not None:
-            want_d_src = [t is not None for t in given_src]
-        # the d_src arrays of all bound scales are views of ONE allocation: the library accumulates into them (float atomics), so every
-        # backward starts by clearing them -- one fill kernel instead of one per scale
-        want_src = [bool(want_d_src[s] if isinstance(want_d_src, (list, tuple)) else want_d_src) for s in range(S)]
-        src_numel = [B * 3 * n_src * int(disps[s].shape[2]) * int(disps[s].shape[3]) if want_src[s] else 0 for s in range(S)]
-        self._d_src_all = torch.zeros((sum(src_numel),), dtype=torch.float32, device=dev) if any(want_src) and given_src is None else None
-        src_off = 0
+            masks = _devs(masks, "masks", 4)
         for s in range(S):
             h, w = disps[s].shape[2:]
-            if hwc:
-                ok = tuple(tgt_pyr[s].shape) == (B, 1, h, w, 3) and tuple(src_pyr[s].shape) == (B, n_src, h, w, 3)
-            else:
-                ok = tuple(tgt_pyr[s].shape) == (B, 3, h, w) and tuple(src_pyr[s].shape) == (B, 3 * n_src, h, w)
-            if not ok or tuple(disps[s].shape) != (B, 1, h, w):
+            want = ((B, 1, h, w, 3), (B, n_src, h, w, 3)) if hwc else ((B, 3, h, w), (B, 3 * n_src, h, w))
+            if (tuple(tgt_pyr[s].shape), tuple(src_pyr[s].shape)) != want or tuple(disps[s].shape) != (B, 1, h, w):
                 raise TypeError("scale %d: expected tgt (B,3,h,w), src (B,3*n_src,h,w) [hwc: (B,1,h,w,3), (B,n_src,h,w,3)], "
                                 "disp (B,1,h,w)" % s)
-            d.H[s], d.W[s] = h, w
-            d.tgt[s], d.src[s], d.disp[s] = tgt_pyr[s].data_ptr(), src_pyr[s].data_ptr(), disps[s].data_ptr()
-            d_disps.append(own("d_disps", s, disps[s].shape))
-            d.d_disp[s] = d_disps[-1].data_ptr()
-            if use_masks:
-                if tuple(masks[s].shape) != (B, n_src, h, w):
-                    raise TypeError("masks[%d] must be (B,n_src,h,w)" % s)
-                d.mask_logits[s] = masks[s].data_ptr()
-                d_masks.append(own("d_masks", s, masks[s].shape))
-                d.d_mask[s] = d_masks[-1].data_ptr()
-            # (want_d_src: True, or one flag per scale -- SfmLossDesc.d_src[s] may be NULL for any scale)
-            if want_src[s] and given_src is not None:
-                d_srcs.append(own("d_srcs", s, (B, 3 * n_src, h, w)))
-                d.d_src[s] = d_srcs[-1].data_ptr()
-            elif want_src[s]:      # always planar
-                d_srcs.append(self._d_src_all[src_off:src_off + src_numel[s]].view(B, 3 * n_src, h, w))
-                src_off += src_numel[s]
-                d.d_src[s] = d_srcs[-1].data_ptr()
-            else:
-                d_srcs.append(None)
-            if want_warped:     # always planar
-                warped.append(own("warped", s, (B, n_src, 3, h, w)))
-                d.warped[s] = warped[-1].data_ptr()
-        d_poses = []
+            if use_masks and tuple(masks[s].shape) != (B, n_src, h, w):
+                raise TypeError("masks[%d] must be (B,n_src,h,w)" % s)
         for i in range(n_src):
             if tuple(poses[i].shape) != (B, 6):
                 raise TypeError("poses[%d] must be (B,6)" % i)
-            d.pose[i] = poses[i].data_ptr()
-            d_poses.append(own("d_poses", i, poses[i].shape))
-            d.d_pose[i] = d_poses[-1].data_ptr()
-        nbytes = lib.sfm_loss_workspace_bytes(C.byref(d)) if B > 0 else 256
-        if nbytes == 0:
-            check(lib.sfm_loss_fwd(C.byref(d), None, None, 0, None))   # re-run the validation for its message
-            raise ValueError(_lib.last_error() or "invalid loss descriptor")
-        # the workspace as include/sfmwarp.h states it: sfm_loss_workspace_bytes bytes on a 256-byte boundary, content undefined
-        # (a fresh torch allocation starts on a 512-byte boundary; should an allocator ever hand out less, 256 spare bytes absorb it)
-        if buffers.get("ws") is not None:
-            self.ws = buffers["ws"]
-            if not isinstance(self.ws, torch.Tensor) or self.ws.device != dev or not self.ws.is_contiguous():
-                raise TypeError("buffers['ws']: expected a contiguous tensor on %s" % (dev,))
-            self._ws_ptr, self._ws_bytes = self.ws.data_ptr(), self.ws.numel() * self.ws.element_size()
-            if self._ws_ptr % 256 or self._ws_bytes < nbytes:
-                raise ValueError("buffers['ws']: need %d bytes on a 256-byte boundary, got %d bytes at offset %d mod 256"
-                                 % (nbytes, self._ws_bytes, self._ws_ptr % 256))
-        else:
-            self.ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            if self.ws.data_ptr() % 256:
-                self.ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
-            self._ws_ptr = self.ws.data_ptr() + (-self.ws.data_ptr()) % 256
-            self._ws_bytes = nbytes
-        self.loss5 = torch.zeros((5,), dtype=torch.float32, device=dev) if buffers.get("loss5") is None else own("loss5", 0, (5,))
-        self.desc, self.device = d, dev
-        self._desc_ref, self._ws_arg, self._loss5_arg = C.byref(d), C.c_void_p(self._ws_ptr), _p(self.loss5)
-        self.d_disps, self.d_poses, self.d_masks, self.d_srcs = d_disps, d_poses, (d_masks if use_masks else None), \
-            (d_srcs if any(t is not None for t in d_srcs) else None)
-        self.warped = warped if want_warped else None
-        self._keep = (tgt_pyr, src_pyr, intrinsics, disps, poses, masks)
-        return self
+        return tgt_pyr, src_pyr, intrinsics, disps, poses, masks
 
     def rebind(self, intrinsics, disps, poses, masks=None):
         """Points the bound descriptor at other input arrays of the SAME shapes (the network outputs of the next
@@ -444,26 +483,22 @@ class FusedLoss:
         d = self.desc
         old = self._keep
         intrinsics = _dev(intrinsics, "intrinsics", 4)
-        disps = [_dev(t, "disps[%d]" % s, 4) for s, t in enumerate(disps)]
-        poses = [_dev(t, "poses[%d]" % i, 2) for i, t in enumerate(poses)]
+        disps, poses = _devs(disps, "disps", 4), _devs(poses, "poses", 2)
         if intrinsics.shape != old[2].shape or len(disps) != len(old[3]) or len(poses) != len(old[4]) \
                 or any(a.shape != b.shape for a, b in zip(disps, old[3])) or any(a.shape != b.shape for a, b in zip(poses, old[4])):
             raise TypeError("rebind: shapes differ from the bound ones (call bind)")
         if self.exp_reg > 0:
             if masks is None:
                 raise ValueError("exp_reg > 0 needs the explainability logits (masks)")
-            masks = [_dev(t, "masks[%d]" % s, 4) for s, t in enumerate(masks)]
+            masks = _devs(masks, "masks", 4)
             if any(a.shape != b.shape for a, b in zip(masks, old[5])):
                 raise TypeError("rebind: mask shapes differ from the bound ones (call bind)")
-            for s, t in enumerate(masks):
-                d.mask_logits[s] = t.data_ptr()
+            _point(d.mask_logits, masks)
         else:
             masks = None
         d.intrinsics = intrinsics.data_ptr()
-        for s, t in enumerate(disps):
-            d.disp[s] = t.data_ptr()
-        for i, t in enumerate(poses):
-            d.pose[i] = t.data_ptr()
+        _point(d.disp, disps)
+        _point(d.pose, poses)
         self._keep = (old[0], old[1], intrinsics, disps, poses, masks)
         return self
 
@@ -477,15 +512,11 @@ class FusedLoss:
                 if t is not None:
                     t.zero_()
 
-    def _launch(self, fn, *mid):
-        """One call through the C ABI on the device's current stream.  The argument objects that never change between
-        calls are built once per bind (a step is 70 us of GPU time: the host side of a call has to stay well below)."""
-        idx = self.device.index
-        if torch.cuda.current_device() == idx:
-            check(fn(self._desc_ref, *mid, self._ws_arg, self._ws_bytes, _stream(idx)))
-        else:
-            with torch.cuda.device(self.device):
-                check(fn(self._desc_ref, *mid, self._ws_arg, self._ws_bytes, _stream(idx)))
+    def _loss5(self, out):
+        """(the array that receives the five scalars, its pointer argument): `out` if the caller gave one, else self.loss5.  The
+        argument objects that never change between calls are built once per bind (a step is 70 us of GPU time: the host side of
+        a call has to stay well below)."""
+        return (self.loss5, self._loss5_arg) if out is None else (out, C.c_void_p(out.data_ptr()))
 
     def step_from_frames(self, tgt_full, src_full, grad=True, out=None):
         """One step from the FULL-RESOLUTION frames in one call through the C ABI (sfm_step_fwd_bwd / sfm_step_fwd): both pyramids
@@ -493,26 +524,20 @@ class FusedLoss:
         tgt_full (B,3,H,W), src_full (B,3*n_src,H,W): float32, contiguous, on the bound device -- the CALLER vouches for that
         (links.SFMLearnerLoss validates once per set of arrays); nothing is checked here but what the library checks itself."""
         self._zero_d_src()
-        loss5 = self.loss5 if out is None else out
-        fn = lib.sfm_step_fwd_bwd if grad else lib.sfm_step_fwd
-        l5 = self._loss5_arg if out is None else C.c_void_p(out.data_ptr())
-        idx = self.device.index
-        if torch.cuda.current_device() == idx:
-            check(fn(tgt_full.data_ptr(), src_full.data_ptr(), self._desc_ref, l5, self._ws_arg, self._ws_bytes, _stream(idx)))
-        else:
-            with torch.cuda.device(self.device):
-                check(fn(tgt_full.data_ptr(), src_full.data_ptr(), self._desc_ref, l5, self._ws_arg, self._ws_bytes, _stream(idx)))
+        loss5, l5 = self._loss5(out)
+        _launch(self.device, lib.sfm_step_fwd_bwd if grad else lib.sfm_step_fwd, tgt_full.data_ptr(), src_full.data_ptr(),
+                self._desc_ref, l5, self._ws_arg, self._ws_bytes)
         return loss5
 
     def forward(self, out=None):
         """`out`: as for forward_backward."""
-        loss5 = self.loss5 if out is None else out
-        self._launch(lib.sfm_loss_fwd, self._loss5_arg if out is None else _p(out))
+        loss5, l5 = self._loss5(out)
+        _launch(self.device, lib.sfm_loss_fwd, self._desc_ref, l5, self._ws_arg, self._ws_bytes)
         return loss5
 
     def backward(self, gy=1.0):
         self._zero_d_src()
-        self._launch(lib.sfm_loss_bwd, float(gy))
+        _launch(self.device, lib.sfm_loss_bwd, self._desc_ref, float(gy), self._ws_arg, self._ws_bytes)
         return self.d_disps, self.d_poses, self.d_masks, self.d_srcs
 
     def forward_backward(self, out=None, variant=0):
@@ -520,8 +545,8 @@ class FusedLoss:
         (lets a caller keep a log of the steps of a reporting interval and reduce it across ranks once).
         `variant`: development hook (sfm_loss_variant): 3 = the kernels read their header from the argument struct."""
         self._zero_d_src()
-        loss5 = self.loss5 if out is None else out
+        loss5, l5 = self._loss5(out)
         if variant:
             check(lib.sfm_loss_variant(int(variant)))
-        self._launch(lib.sfm_loss_fwd_bwd, self._loss5_arg if out is None else _p(out))
+        _launch(self.device, lib.sfm_loss_fwd_bwd, self._desc_ref, l5, self._ws_arg, self._ws_bytes)
         return loss5

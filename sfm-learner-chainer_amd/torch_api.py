@@ -28,14 +28,12 @@ import torch
 from torch import Tensor
 
 from . import _lib, ops
-from ._lib import SfmLossDesc, check, lib
-from .links import HWC_MAX_PIXELS, parse_dict
+from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "scale_arrays_into"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
-_FLOATS = (torch.float32, torch.bfloat16, torch.float16)
 
 
 def _round(n):
@@ -44,13 +42,19 @@ def _round(n):
 
 def _grad_spans(disps, poses, masks):
     """[offset0, numel0, offset1, numel1, ...] of the unit-gradient arrays d_disp[s], d_pose[i], d_mask[s] (in that order) inside
-    the one buffer the loss op returns, and that buffer's length in floats."""
-    spans, off = [], 0
+    the one buffer the loss op returns, that buffer's length in floats, and the arrays' shapes."""
+    spans, off, shapes = [], 0, []
     for t in list(disps) + list(poses) + list(masks):
         n = t.numel()
         spans += [off, n]
         off += _round(n)
-    return spans, off
+        shapes.append(tuple(t.shape))
+    return spans, off, shapes
+
+
+def _views(buf, spans, shapes):
+    """the arrays that lie at `spans` in the flat buffer `buf`"""
+    return [buf[o:o + n].view(shape) for o, n, shape in zip(spans[0::2], spans[1::2], shapes)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -59,13 +63,7 @@ def _grad_spans(disps, poses, masks):
 def _launch_scale(xp, yp, numel, gy, device):
     n = len(numel)
     ptr = C.c_void_p * n
-    args = (ptr(*xp), ptr(*yp), (C.c_longlong * n)(*numel), n, C.c_void_p(gy.data_ptr()))
-    idx = device.index
-    if torch.cuda.current_device() == idx:
-        check(lib.sfm_scale_arrays(*args, ops._stream(idx)))
-    else:
-        with torch.cuda.device(device):
-            check(lib.sfm_scale_arrays(*args, ops._stream(idx)))
+    ops._launch(device, lib.sfm_scale_arrays, ptr(*xp), ptr(*yp), (C.c_longlong * n)(*numel), n, C.c_void_p(gy.data_ptr()))
 
 
 def _gy(gy):
@@ -104,6 +102,16 @@ def _check_spans(spans, n):
             raise TypeError("scale_arrays: span %d = (offset %d, numel %d) lies outside x's %d elements" % (k // 2, o, m, n))
 
 
+def _scaled(x, spans, gy):
+    """sfmwarp::scale_arrays on checked arguments (the eager backward calls it directly): one launch, none for no spans."""
+    out = torch.empty_like(x)
+    if spans:
+        xb, yb = x.data_ptr(), out.data_ptr()
+        offs = spans[0::2]
+        _launch_scale([xb + 4 * o for o in offs], [yb + 4 * o for o in offs], spans[1::2], gy, x.device)
+    return out
+
+
 @torch.library.custom_op("sfmwarp::scale_arrays", mutates_args=())
 def _scale_arrays_op(x: Tensor, spans: list[int], gy: Tensor) -> Tensor:
     """x: a flat float32 device buffer that holds up to 32 arrays at spans = [offset0, numel0, offset1, numel1, ...] (floats) ->
@@ -112,12 +120,7 @@ def _scale_arrays_op(x: Tensor, spans: list[int], gy: Tensor) -> Tensor:
     x, gy = ops._dev(x, "x", 1), _gy(gy)
     if gy.device != x.device:
         raise TypeError("scale_arrays: gy lives on %s, x on %s" % (gy.device, x.device))
-    out = torch.empty_like(x)
-    if spans:
-        xb, yb = x.data_ptr(), out.data_ptr()
-        offs, numel = spans[0::2], spans[1::2]
-        _launch_scale([xb + 4 * o for o in offs], [yb + 4 * o for o in offs], numel, gy, x.device)
-    return out
+    return _scaled(x, spans, gy)
 
 
 @_scale_arrays_op.register_fake
@@ -148,27 +151,18 @@ def _plan(B, H, W, n_src, disps, masks, poses, cfg):
     p = _PLANS.get(key)
     if p is not None:
         return p
-    smooth_reg, exp_reg, ssim_rate, smooth_mode, projection, norm_batch = cfg
     p = _Plan()
-    p.hwc = H * W < HWC_MAX_PIXELS
-    d = SfmLossDesc()
-    d.B, d.norm_B, d.n_src, d.n_scales = B, norm_batch, n_src, S
-    d.smooth_reg, d.exp_reg, d.ssim_rate, d.smooth_mode = smooth_reg, exp_reg, ssim_rate, smooth_mode
-    d.image_layout = _lib.SFM_LAYOUT_HWC if p.hwc else _lib.SFM_LAYOUT_PLANAR
-    d.projection = projection
+    layout = ops.layout_for(H, W)
+    p.hwc = layout == "hwc"
+    d = ops.loss_desc(B, cfg[5], n_src, [shape[2:] for shape in shapes], cfg[:5], layout)
     for s in range(S):
-        d.H[s], d.W[s] = shapes[s][2], shapes[s][3]
         d.tgt[s] = d.src[s] = d.disp[s] = d.d_disp[s] = _FAKE
         if masks:
             d.mask_logits[s] = d.d_mask[s] = _FAKE
     for i in range(n_src):
         d.pose[i] = d.d_pose[i] = _FAKE
     d.intrinsics = _FAKE
-    nbytes = lib.sfm_loss_workspace_bytes(C.byref(d)) if B > 0 else 256
-    if nbytes == 0:
-        check(lib.sfm_loss_fwd(C.byref(d), None, None, 0, None))   # re-run the validation for its message
-        raise ValueError(_lib.last_error() or "invalid loss descriptor")
-    p.desc, p.ws_bytes = bytes(d), nbytes
+    p.desc, p.ws_bytes = bytes(d), ops.workspace_bytes(d)
     # scratch: the pyramids (hwc: every scale of both; planar: scales 1.. -- scale 0 is the frame itself), then the workspace
     off, p.tgt_off, p.src_off = 0, [], []
     for s in range(S):
@@ -182,8 +176,8 @@ def _plan(B, H, W, n_src, disps, masks, poses, cfg):
             p.tgt_off.append(None)
             p.src_off.append(None)
     p.ws_off = off
-    p.scratch = off + _round(nbytes // 4) + _ALIGN    # + the slack to put the workspace on a 256-byte boundary
-    p.spans, p.grad_floats = _grad_spans(disps, poses, masks)
+    p.scratch = off + _round(p.ws_bytes // 4) + _ALIGN    # + the slack to put the workspace on a 256-byte boundary
+    p.spans, p.grad_floats, _ = _grad_spans(disps, poses, masks)
     if len(_PLANS) >= _MAX_PLANS:
         _PLANS.pop(next(iter(_PLANS)))            # the oldest configuration (e.g. an epoch's last, smaller batch)
     _PLANS[key] = p
@@ -231,25 +225,14 @@ def _run_loss(tgt, src, K, disps, poses, masks, cfg, grad):
         _desc_hook(bytes(d))
     ws = C.c_void_p(base + 4 * p.ws_off)
     l5 = C.c_void_p(loss5.data_ptr())
-    idx = dev.index
-    guard = torch.cuda.device(dev) if torch.cuda.current_device() != idx else None
-    if guard is not None:
-        guard.__enter__()
-    try:
-        st = ops._stream(idx)
-        if p.hwc:
-            fn = lib.sfm_step_fwd_bwd if grad else lib.sfm_step_fwd
-            check(fn(tgt.data_ptr(), src.data_ptr(), C.byref(d), l5, ws, p.ws_bytes, st))
-        else:
-            for x, pyr, G in ((tgt, d.tgt, 3), (src, d.src, 3 * n_src)):
-                if S > 1:
-                    ptrs = (C.c_void_p * S)(*[pyr[s] for s in range(S)])
-                    check(lib.sfm_pyramid_fwd(x.data_ptr(), ptrs, B, G, H, W, S, st))
-            fn = lib.sfm_loss_fwd_bwd if grad else lib.sfm_loss_fwd
-            check(fn(C.byref(d), l5, ws, p.ws_bytes, st))
-    finally:
-        if guard is not None:
-            guard.__exit__(None, None, None)
+    if p.hwc:
+        fn = lib.sfm_step_fwd_bwd if grad else lib.sfm_step_fwd
+        ops._launch(dev, fn, tgt.data_ptr(), src.data_ptr(), C.byref(d), l5, ws, p.ws_bytes)
+    else:
+        for x, pyr, G in ((tgt, d.tgt, 3), (src, d.src, 3 * n_src)):
+            if S > 1:
+                ops._launch(dev, lib.sfm_pyramid_fwd, x.data_ptr(), (C.c_void_p * S)(*pyr[:S]), B, G, H, W, S)
+        ops._launch(dev, lib.sfm_loss_fwd_bwd if grad else lib.sfm_loss_fwd, C.byref(d), l5, ws, p.ws_bytes)
     return loss5, g
 
 
@@ -272,15 +255,14 @@ def _loss_op(tgt_img: Tensor, src_imgs: Tensor, intrinsics: Tensor, disps: list[
 @_loss_op.register_fake
 def _(tgt_img, src_imgs, intrinsics, disps, poses, masks, smooth_reg, exp_reg, ssim_rate, smooth_mode, projection, norm_batch,
       grad):
-    _, n = _grad_spans(disps, poses, masks)
+    n = _grad_spans(disps, poses, masks)[1]
     f = dict(dtype=torch.float32, device=tgt_img.device)
     return [torch.empty((), **f), torch.empty((4,), **f), torch.empty((n if grad else 0,), **f)]
 
 
 def _setup_context(ctx, inputs, output):
     disps, poses, masks = inputs[3], inputs[4], inputs[5]
-    ctx.spans, _ = _grad_spans(disps, poses, masks)
-    ctx.shapes = [tuple(t.shape) for t in list(disps) + list(poses) + list(masks)]
+    ctx.spans, _, ctx.shapes = _grad_spans(disps, poses, masks)
     ctx.counts = (len(disps), len(poses), len(masks))
     ctx.grad = inputs[12]
     ctx.mark_non_differentiable(output[1], output[2])
@@ -293,22 +275,11 @@ def _backward(ctx, grads):
     if not ctx.grad:        # no prediction required a gradient (only an image or the intrinsics did): none flows anywhere
         return (None, None, None, [None] * S, [None] * n, [None] * m, None, None, None, None, None, None, None)
     gy = grads[0].to(torch.float32)
-    out = torch.ops.sfmwarp.scale_arrays(unit, ctx.spans, gy)
-    sp = ctx.spans
-    views = [out[sp[2 * k]:sp[2 * k] + sp[2 * k + 1]].view(shape) for k, shape in enumerate(ctx.shapes)]
+    views = _views(torch.ops.sfmwarp.scale_arrays(unit, ctx.spans, gy), ctx.spans, ctx.shapes)
     return (None, None, None, views[:S], views[S:S + n], views[S + n:], None, None, None, None, None, None, None)
 
 
 _loss_op.register_autograd(_backward, setup_context=_setup_context)
-
-
-def _scaled(unit, spans, shapes, gy):
-    """Eager backward: `unit` times the device scalar gy into a fresh buffer (one sfm_scale_arrays launch), as views of the arrays."""
-    out = torch.empty_like(unit)
-    xb, yb = unit.data_ptr(), out.data_ptr()
-    offs = spans[0::2]
-    _launch_scale([xb + 4 * o for o in offs], [yb + 4 * o for o in offs], spans[1::2], _gy(gy), unit.device)
-    return [out[o:o + n].view(shape) for o, n, shape in zip(offs, spans[1::2], shapes)]
 
 
 class _LossFunction(torch.autograd.Function):
@@ -325,8 +296,7 @@ class _LossFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)              # (no zero-filled gradient for `terms`: one fill kernel less per step)
         ctx.save_for_backward(unit)                   # (freed by a backward without retain_graph, like any saved tensor)
         ctx.grad = grad
-        ctx.spans, _ = _grad_spans(disps, poses, masks)
-        ctx.shapes = [a.shape for a in arrays]
+        ctx.spans, _, ctx.shapes = _grad_spans(disps, poses, masks)
         return loss5[0], terms
 
     @staticmethod
@@ -334,23 +304,14 @@ class _LossFunction(torch.autograd.Function):
         (unit,) = ctx.saved_tensors
         if g_total is None or not ctx.grad:     # (not ctx.grad: only an image or the intrinsics required a gradient)
             return (None,) * (7 + len(ctx.shapes))
-        return (None,) * 7 + tuple(_scaled(unit, ctx.spans, ctx.shapes, g_total.to(torch.float32)))
+        return (None,) * 7 + tuple(_views(_scaled(unit, ctx.spans, _gy(g_total.to(torch.float32))), ctx.spans, ctx.shapes))
 
 
 def _dev_float(t, name, ndim=None):
     """A differentiable network output: float32, bfloat16 or float16 on a ROCm device -> float32, contiguous (casts and copies are
     recorded by autograd, so the gradient returns in the input's dtype and layout)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s: expected a torch.Tensor on a ROCm device, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise TypeError("%s: CPU arrays are not supported by this build (GPU-only, no CPU fallback)" % name)
-    if t.dtype not in _FLOATS:
-        raise TypeError("%s: expected dtype float32, bfloat16 or float16, got %s" % (name, t.dtype))
-    if ndim is not None and t.dim() != ndim:
-        raise TypeError("%s: expected ndim == %d, got %d" % (name, ndim, t.dim()))
-    if t.dtype != torch.float32:
-        t = t.to(torch.float32)
-    return t if t.is_contiguous() else t.contiguous()
+    t = ops._dev(t, name, ndim, ops.FLOATS)
+    return t if t.dtype == torch.float32 else t.to(torch.float32)
 
 
 def _poses(pred_poses, B, n_src):
@@ -391,10 +352,7 @@ def sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred
     With grad mode on and any prediction requiring grad, ONE fused launch computes the loss and its gradients for gy = 1; backward
     scales them by the upstream gradient on the device (so loss scaling, GradScaler and graph capture work, and no call syncs).
     Gradients are per call: several forwards before one backward each keep their own."""
-    if smooth_mode not in _lib.SMOOTH_MODES:
-        raise ValueError("smooth_mode must be one of %s" % sorted(k for k in _lib.SMOOTH_MODES if k))
-    if projection not in _lib.PROJECTIONS:
-        raise ValueError("projection must be one of %s" % sorted(k for k in _lib.PROJECTIONS if k))
+    smooth_mode, projection = _lib.smooth_mode_id(smooth_mode), _lib.projection_id(projection)
     tgt = ops._dev(tgt_img, "tgt_img", 4)
     src = ops._dev(src_imgs, "src_imgs", 5)
     B, n_src, c, H, W = src.shape
@@ -429,7 +387,7 @@ def sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred
         if t.device != tgt.device:
             raise TypeError("every array must live on %s, one is on %s" % (tgt.device, t.device))
     grad = torch.is_grad_enabled() and any(t.requires_grad for t in disps + poses + masks)
-    cfg = (float(smooth_reg or 0.0), exp_reg, float(ssim_rate or 0.0), _lib.SMOOTH_MODES[smooth_mode], _lib.PROJECTIONS[projection],
+    cfg = (float(smooth_reg or 0.0), exp_reg, float(ssim_rate or 0.0), smooth_mode, projection,
            int(norm_batch if norm_batch is not None else B))
     stacked = src.view(B, 3 * n_src, H, W)
     if torch.compiler.is_compiling():
@@ -449,7 +407,7 @@ class SFMLearnerLoss(torch.nn.Module):
         self.n_sources = config['seq_len'] - 1
         self.smooth_reg = config['smooth_reg']
         self.exp_reg = config['exp_reg']
-        self.ssim_rate = parse_dict(config, 'ssim_rate', 0.0)
+        self.ssim_rate = config['ssim_rate'] if 'ssim_rate' in config else 0.0     # models/base_model.py:24-25, 39
         self.smooth_mode = smooth_mode
         self.projection = projection
         self._last = None

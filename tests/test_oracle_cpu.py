@@ -27,7 +27,7 @@ def test_interp_sampler_restated_bit_exact(path):
 
 def test_golden_fixture_set_is_complete():
     names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLD, "*.npz")))
-    assert names == ["euler_odom_util.npz", "interp_sampler_border.npz", "interp_sampler_c1.npz",
+    assert names == ["euler_odom_util.npz", "host_plans.npz", "interp_sampler_border.npz", "interp_sampler_c1.npz",
                      "interp_sampler_c5.npz", "interp_sampler_kitti_s3.npz", "interp_sampler_ragged.npz",
                      "interp_sampler_small.npz", "intrinsics_aug.npz",
                      "plan_table.npz"]      # (the launch plans of the fused loss: tests/test_plan_cpu.py)
