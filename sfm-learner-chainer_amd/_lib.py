@@ -1,4 +1,4 @@
-"""ctypes binding of libsfmwarp.so (include/sfmwarp.h).  No torch types cross this boundary:
+"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h).  No torch types cross this boundary:
 every tensor is handed over as a raw device pointer plus explicit sizes.
 
 The library is REQUIRED: there is no CPU or PyTorch fallback.  If it is missing, importing
@@ -16,6 +16,7 @@ import torch  # noqa: F401
 
 SFM_MAX_SCALES = 8
 SFM_MAX_SRC = 8
+SFM_RESIZE_MAX_TERMS = 8
 SFM_ABI_VERSION = 6
 SFM_LAYOUT_PLANAR, SFM_LAYOUT_HWC = 0, 1
 SFM_PROJECTION_FAST, SFM_PROJECTION_REFERENCE_ORDER = 0, 1
@@ -102,6 +103,11 @@ SYMBOLS = {
     "sfm_pyramid_pair_hwc_fwd": (_I, [_FP, _FP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I, _I, _I, _I, _I, _V]),
 }
 
+# every symbol declared in include/sfmwarp_ext.h (entry points newer than the set above)
+EXT_SYMBOLS = {
+    "sfm_resize_bwd": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _FP, _I, _I, _I, _I, _V]),
+}
+
 
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
@@ -113,7 +119,7 @@ def _load():
             "libsfmwarp.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

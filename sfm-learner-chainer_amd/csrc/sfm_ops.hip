@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "sfm_common.h"
+#include "sfmwarp_ext.h"
 
 #define SFM_REQUIRE(cond, code, ...) \
   do {                               \
@@ -571,6 +572,69 @@ __global__ void resize_fwd_kernel(const float* __restrict__ x, float* __restrict
   const float u = oW > 1 ? resize_coord(ox, (double)(W - 1) / (double)(oW - 1)) : 0.f;
   const float v = oH > 1 ? resize_coord(oy, (double)(H - 1) / (double)(oH - 1)) : 0.f;
   y[(size_t)nc * oH * oW + j] = resize_read(resize_taps(u, v, H, W), x + (size_t)nc * H * W, W);
+}
+
+// ------------------------------------------------------------------------------------------
+// Backward of F.resize_images (models/disp_net.py:14,105,111,117) and, with several terms, the adjoint of the pyramid's loop head
+// (models/base_model.py:70-72): gx = sum_k R_k^T gy[k], as a GATHER -- one thread per INPUT element adds up, term after term, the
+// outputs whose taps touch it, in ascending (oy, ox).  No atomics, one fixed summation order, one coalesced store per thread.
+//
+// Which outputs touch input index i along one axis (n inputs, `on` outputs): tap0(o) = resize_tap0(resize_coord(o, step), n) does
+// not decrease with o (a double product rounded to float, floored and clamped: each step is monotone), and tap1 = min(tap0 + 1,
+// n - 1), so they are the contiguous range [first(i - 1), first(i + 1)) with first(k) = the first o whose tap0 is >= k.  first()
+// only ESTIMATES that index from k / step; the forward's own tap0, evaluated on the candidates, settles it, and inside the range
+// each output's weight is picked by comparing the taps resize_taps returns with i.  No inverse formula decides membership: one
+// ulp there would drop a contribution or count it twice.
+// ------------------------------------------------------------------------------------------
+struct ResizeBwdArgs {
+  const float* gy[SFM_RESIZE_MAX_TERMS];
+  float* gx;
+  long long total;                                        // N C H W
+  int oH[SFM_RESIZE_MAX_TERMS], oW[SFM_RESIZE_MAX_TERMS];
+  // the forward's steps (resize_fwd_kernel, PyramidArgs) and their reciprocals (0 for a step of 0), all formed in double on the host
+  double step_u[SFM_RESIZE_MAX_TERMS], step_v[SFM_RESIZE_MAX_TERMS], inv_u[SFM_RESIZE_MAX_TERMS], inv_v[SFM_RESIZE_MAX_TERMS];
+  int H, W, n_terms;
+};
+
+// the first o in [0, on] with resize_tap0(resize_coord(o, step), n) >= k (on: there is none)
+__device__ __forceinline__ int resize_first_at(const int k, const int n, const int on, const double step, const double inv_step) {
+  if (k <= 0) return 0;
+  if (k > max(n - 2, 0)) return on;              // tap0 never exceeds n - 2
+  int o = (int)fmin(ceil((double)k * inv_step), (double)on);
+  while (o > 0 && resize_tap0(resize_coord(o - 1, step), n) >= k) --o;
+  while (o < on && resize_tap0(resize_coord(o, step), n) < k) ++o;
+  return o;
+}
+
+__global__ void __launch_bounds__(256) resize_bwd_kernel(const ResizeBwdArgs A) {
+#pragma clang fp contract(off)
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= A.total) return;
+  const int H = A.H, W = A.W;
+  const long long HW = (long long)H * W;
+  const long long nc = j / HW, r = j - nc * HW;
+  const int iy = HW < (1ll << 31) ? (int)((unsigned)r / (unsigned)W) : (int)(r / W);
+  const int ix = (int)(r - (long long)iy * W);
+  float acc = 0.f;
+  for (int k = 0; k < A.n_terms; ++k) {
+    const int oH = A.oH[k], oW = A.oW[k];
+    const double su = A.step_u[k], sv = A.step_v[k];
+    const int x0 = resize_first_at(ix - 1, W, oW, su, A.inv_u[k]), x1 = resize_first_at(ix + 1, W, oW, su, A.inv_u[k]);
+    const int y0 = resize_first_at(iy - 1, H, oH, sv, A.inv_v[k]), y1 = resize_first_at(iy + 1, H, oH, sv, A.inv_v[k]);
+    const float* g = A.gy[k] + nc * ((long long)oH * oW);
+    for (int oy = y0; oy < y1; ++oy) {
+      const float v = resize_coord(oy, sv);
+      for (int ox = x0; ox < x1; ++ox) {
+        // the forward's taps and weights of output (oy, ox); of each axis' two, the one that lands on this element (the other
+        // adds an exact 0; with one input row or column both land here and add up to the forward's 1 + 0)
+        const ResizeTap t = resize_taps(resize_coord(ox, su), v, H, W);
+        const float wu = (t.u0 == ix ? t.wu0 : 0.f) + (t.u1 == ix ? t.wu1 : 0.f);
+        const float wv = (t.v0 == iy ? t.wv0 : 0.f) + (t.v1 == iy ? t.wv1 : 0.f);
+        acc = acc + g[(long long)oy * oW + ox] * (wv * wu);      // gy * (wv * wu): the weights' product first
+      }
+    }
+  }
+  A.gx[j] = acc;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1237,6 +1301,36 @@ int sfm_resize_fwd(const float* x, float* y, int N, int C, int H, int W, int oH,
   SFM_REQUIRE((long long)N * C <= 65535, SFM_ERR_SHAPE, "sfm_resize_fwd: N*C=%lld > 65535", (long long)N * C);
   hipLaunchKernelGGL(resize_fwd_kernel, dim3((oH * oW + 255) / 256, N * C), dim3(256), 0, (hipStream_t)stream, x, y, H, W, oH, oW);
   return check_launch("sfm_resize_fwd");
+}
+
+int sfm_resize_bwd(const float* const* gy, const int* oH, const int* oW, int n_terms, float* gx, int N, int C, int H, int W,
+                   void* stream) {
+  const char* who = "sfm_resize_bwd";
+  SFM_REQUIRE(gy && oH && oW && (gx || N == 0), SFM_ERR_NULL, "%s: NULL pointer", who);
+  SFM_REQUIRE(n_terms >= 1 && n_terms <= SFM_RESIZE_MAX_TERMS, SFM_ERR_SHAPE, "%s: n_terms=%d, need 1..%d", who, n_terms,
+              SFM_RESIZE_MAX_TERMS);
+  SFM_REQUIRE(N >= 0 && C >= 1 && H >= 1 && W >= 1, SFM_ERR_SHAPE, "%s: bad shape N=%d C=%d H=%d W=%d", who, N, C, H, W);
+  ResizeBwdArgs A;
+  A.gx = gx, A.H = H, A.W = W, A.n_terms = n_terms;
+  const unsigned __int128 planes = (unsigned __int128)((long long)N * C), limit = (unsigned __int128)1 << 40;
+  unsigned __int128 read = 0;
+  for (int k = 0; k < n_terms; ++k) {
+    SFM_REQUIRE(oH[k] >= 1 && oW[k] >= 1, SFM_ERR_SHAPE, "%s: term %d is empty (oH=%d oW=%d)", who, k, oH[k], oW[k]);
+    SFM_REQUIRE(N == 0 || gy[k], SFM_ERR_NULL, "%s: gy[%d] is NULL", who, k);
+    A.gy[k] = gy[k], A.oH[k] = oH[k], A.oW[k] = oW[k];
+    // numpy.linspace's step, as resize_fwd_kernel and pyramid_setup form it; one output: the forward samples at 0
+    A.step_u[k] = oW[k] > 1 ? (double)(W - 1) / (double)(oW[k] - 1) : 0.0;
+    A.step_v[k] = oH[k] > 1 ? (double)(H - 1) / (double)(oH[k] - 1) : 0.0;
+    A.inv_u[k] = A.step_u[k] > 0.0 ? 1.0 / A.step_u[k] : 0.0;
+    A.inv_v[k] = A.step_v[k] > 0.0 ? 1.0 / A.step_v[k] : 0.0;
+    read += planes * (unsigned __int128)((long long)oH[k] * oW[k]);
+  }
+  const unsigned __int128 total = planes * (unsigned __int128)((long long)H * W);
+  SFM_REQUIRE(total < limit && read < limit, SFM_ERR_SHAPE, "%s: too large", who);
+  if (total == 0) return SFM_OK;   // empty batch: nothing to do
+  A.total = (long long)total;
+  hipLaunchKernelGGL(resize_bwd_kernel, dim3((unsigned)((A.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+  return check_launch(who);
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@ signatures, running on the HIP kernels of libsfmwarp.so.
   spatial_transformer_sampler(x, grid)             F.spatial_transformer_sampler as called at models/transform.py:189
   proj_tgt_to_src(vec, K, N)                       models/transform.py:64-91
   projective_inverse_warp(imgs, depthes, poses, K) models/transform.py:156-193
-  resize_images(x, output_shape)                   F.resize_images as called at models/base_model.py:71-72
+  resize_images(x, output_shape)                   F.resize_images as called at models/base_model.py:71-72 and, differentiated,
+  ResizeImages                                     at models/disp_net.py:14,105,111,117
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ from .chainer_surface import Function, Variable, argument, as_array, type_check
 
 __all__ = ["SpatialTransformerSamplerInterp", "spatial_transformer_sampler_interp", "SpatialTransformerSampler",
            "spatial_transformer_sampler", "ProjTgtToSrc", "proj_tgt_to_src", "ProjectiveInverseWarp",
-           "projective_inverse_warp", "resize_images", "DispActivation", "disp_activation"]
+           "projective_inverse_warp", "ResizeImages", "resize_images", "DispActivation", "disp_activation"]
 
 
 def _sampler_type_check(in_types):
@@ -150,10 +151,31 @@ def projective_inverse_warp(imgs, depthes, poses, K):
     return ProjectiveInverseWarp()(imgs, depthes, poses, K)
 
 
+class ResizeImages(Function):
+    """F.resize_images: bilinear, align-corners.  x (N,C,H,W) -> (N,C,out_H,out_W); backward: the adjoint, as a gather."""
+
+    def __init__(self, output_shape):
+        self.out_H, self.out_W = int(output_shape[0]), int(output_shape[1])
+
+    def check_type_forward(self, in_types):
+        type_check.expect(in_types.size() == 1)
+        type_check.expect(in_types[0].dtype.char == 'f', in_types[0].ndim == 4)
+
+    def forward_gpu(self, inputs):
+        x, = inputs
+        return ops.resize(x, (self.out_H, self.out_W)),
+
+    def backward_gpu(self, inputs, grad_outputs):
+        x, = inputs
+        gy, = grad_outputs
+        return ops.resize_bwd(gy, x.shape[2:]),
+
+
 def resize_images(x, output_shape):
-    """F.resize_images(x, (out_H, out_W)): bilinear, align-corners; returns a Variable whose
-    `.data` is what the reference takes (base_model.py:71-72)."""
-    return Variable(ops.resize(as_array(x), output_shape), requires_grad=False)
+    """F.resize_images(x, (out_H, out_W)): bilinear, align-corners; returns a Variable whose `.data` is what the reference
+    takes (base_model.py:71-72).  Differentiable as in the reference (models/disp_net.py:14,105,111,117): the gradient flows
+    to a Variable that requires one; an array or any other Variable gives a result with requires_grad=False."""
+    return ResizeImages(output_shape)(x)
 
 
 class DispActivation(Function):

@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import SfmLossDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "warp_fwd", "warp_bwd", "sampler_fwd", "sampler_bwd",
-           "interp_fwd", "interp_bwd", "resize", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss"]
+           "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -185,6 +185,28 @@ def resize(x, out_hw):
     y = torch.empty((N, Cc, oH, oW), dtype=torch.float32, device=x.device)
     _launch(x.device, lib.sfm_resize_fwd, _p(x), _p(y), N, Cc, H, W, oH, oW)
     return y
+
+
+def resize_bwd(gys, in_hw):
+    """Backward of `resize` (sfm_resize_bwd): gys, one array (N,C,oh,ow) or a list of 1..8 of them with the same N, C and device,
+    each the gradient of a resize of ONE input (N,C,*in_hw) to its own size -> gx (N,C,*in_hw), the sum of their adjoints in one
+    launch.  [d_src[s] for s in scales] of a fused loss -> the gradient of the full-resolution frames.  A gather: no atomics, the
+    same bits on every call."""
+    gys = [gys] if isinstance(gys, torch.Tensor) else list(gys)
+    if not 1 <= len(gys) <= _lib.SFM_RESIZE_MAX_TERMS:
+        raise TypeError("resize_bwd: 1..%d gradient arrays, got %d" % (_lib.SFM_RESIZE_MAX_TERMS, len(gys)))
+    gys = _devs(gys, "gys", 4)
+    N, Cc = gys[0].shape[:2]
+    for k, g in enumerate(gys):
+        if tuple(g.shape[:2]) != (N, Cc) or g.device != gys[0].device:
+            raise TypeError("resize_bwd: gys[%d] is %s on %s, gys[0] %s on %s: N, C and the device must agree"
+                            % (k, tuple(g.shape), g.device, tuple(gys[0].shape), gys[0].device))
+    H, W = int(in_hw[0]), int(in_hw[1])
+    gx = torch.empty((N, Cc, H, W), dtype=torch.float32, device=gys[0].device)
+    sizes = C.c_int * len(gys)
+    _launch(gx.device, lib.sfm_resize_bwd, _ptr_array(gys), sizes(*[g.shape[2] for g in gys]), sizes(*[g.shape[3] for g in gys]),
+            len(gys), _p(gx), N, Cc, H, W)
+    return gx
 
 
 def _pyramid_shapes(n_scales, N, G, H, W, tail=()):

@@ -6,6 +6,8 @@ grad_fn.  This module hands those outputs to libsfmwarp and the gradients it com
   sfm_learner_loss / SFMLearnerLoss   the loss of models/base_model.py:48-124 as a function and as a torch.nn.Module
   projective_inverse_warp             models/transform.py:156-193 (ops.warp_fwd / ops.warp_bwd)
   disp_activation                     models/disp_net.py:104-122 (ops.disp_act_fwd / ops.disp_act_bwd)
+  resize_images / resize_like         F.resize_images as DispNet's decoder differentiates it, models/disp_net.py:11-14,105,111,117
+                                      (ops.resize / ops.resize_bwd)
 
 The loss is two custom operators (torch.library), so that FakeTensor and torch.compile can trace it:
 
@@ -30,7 +32,8 @@ from torch import Tensor
 from . import _lib, ops
 from ._lib import SfmLossDesc, lib
 
-__all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "scale_arrays_into"]
+__all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
+           "scale_arrays_into"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -471,3 +474,29 @@ def disp_activation(xs):
     (ops.disp_act_fwd; backward ops.disp_act_bwd).  float32, bfloat16 or float16 on a ROCm device (the logits of a network under
     autocast): computed and returned in float32, each gradient returned in its input's dtype."""
     return list(_DispAct.apply(*[_dev_float(x, "xs[%d]" % k) for k, x in enumerate(xs)]))
+
+
+class _Resize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, out_hw):
+        ctx.in_hw = tuple(x.shape[2:])
+        return ops.resize(x, out_hw)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.resize_bwd(g.contiguous(), ctx.in_hw), None
+
+
+def resize_images(x, output_shape):
+    """F.resize_images(x, (out_H, out_W)), bilinear and align-corners, as DispNet's decoder calls it (models/disp_net.py:105,111,117):
+    x (N,C,H,W) -> (N,C,out_H,out_W), sampled at the reference's double linspace positions (ops.resize).  The gradient is that
+    map's adjoint, computed as a gather (ops.resize_bwd): no atomics, the same bits on every run.  float32, bfloat16 or float16 on
+    a ROCm device: computed and returned in float32, the gradient returned in the input's dtype."""
+    return _Resize.apply(_dev_float(x, "x", 4), (int(output_shape[0]), int(output_shape[1])))
+
+
+def resize_like(inputs, ref):
+    """models/disp_net.py:11-14: `inputs` resized to the height and width of `ref`; `inputs` itself when they already agree."""
+    if tuple(inputs.shape[2:]) == tuple(ref.shape[2:]):
+        return inputs
+    return resize_images(inputs, ref.shape[2:])

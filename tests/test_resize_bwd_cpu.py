@@ -1,0 +1,194 @@
+"""sfm_resize_bwd without a GPU: the header and the binding declare the same entry points, every rejected call answers with its
+code and message before any HIP call (host pointers that are never dereferenced), the host layer rejects what it must, and the
+NumPy emulation of the kernel's arithmetic (tests/resize_bwd_ref.py) meets the fp64 reference -- exactly where every weight is
+dyadic, within the derived tolerance on the edge shapes of tests/test_resize_bwd_gpu.py."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import resize_bwd_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_lib = importlib.import_module("sfm-learner-chainer_amd._lib")
+ops = importlib.import_module("sfm-learner-chainer_amd.ops")
+functions = importlib.import_module("sfm-learner-chainer_amd.functions")
+surface = importlib.import_module("sfm-learner-chainer_amd.chainer_surface")
+
+FAKE = 0x1000                  # never dereferenced
+WHO = "sfm_resize_bwd: "
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# header and binding
+# ------------------------------------------------------------------------------------------------------------------------
+def test_header_and_binding_declare_the_same_symbols():
+    text = open(os.path.join(ROOT, "include", "sfmwarp_ext.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = sorted(set(re.findall(r"\b(sfm_[a-z0-9_]+)\s*\(", text)))
+    assert declared == sorted(_lib.EXT_SYMBOLS) == ["sfm_resize_bwd"]
+    assert not set(_lib.EXT_SYMBOLS) & set(_lib.SYMBOLS)
+    assert '#include "sfmwarp.h"' in text
+    assert int(re.search(r"#define SFM_RESIZE_MAX_TERMS (\d+)", text).group(1)) == _lib.SFM_RESIZE_MAX_TERMS == 8
+
+
+def test_the_library_exports_them():
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    for name in _lib.EXT_SYMBOLS:
+        assert name in exported, name
+        assert getattr(_lib.lib, name).argtypes == _lib.EXT_SYMBOLS[name][1]
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the raw entry point: what it answers before any HIP call
+# ------------------------------------------------------------------------------------------------------------------------
+def call(gy="ok", oH=(4, 2), oW=(4, 2), n_terms=None, gx=FAKE, N=1, Cc=3, H=8, W=8):
+    """-> (return code, message).  gy: "ok" = one fake device pointer per term, None = a NULL array, or a list (0 = NULL entry)"""
+    n = len(oH) if oH is not None else 2
+    ptrs = [FAKE] * n if gy == "ok" else gy
+    a_gy = (C.c_void_p * len(ptrs))(*[p or None for p in ptrs]) if ptrs is not None else None
+    a_oH = (C.c_int * len(oH))(*oH) if oH is not None else None
+    a_oW = (C.c_int * len(oW))(*oW) if oW is not None else None
+    assert _lib.lib.sfm_pyramid_variant(7) == _lib.ERR_CONFIG          # the message before the call: a known sentinel
+    sentinel = _lib.last_error()
+    rc = _lib.lib.sfm_resize_bwd(a_gy, a_oH, a_oW, n if n_terms is None else n_terms, C.c_void_p(gx) if gx else None, N, Cc, H, W, None)
+    msg = _lib.last_error()
+    return rc, (None if msg == sentinel else msg)
+
+
+@pytest.mark.parametrize("kw", [dict(gy=None), dict(oH=None), dict(oW=None), dict(gx=None)])
+def test_each_null_argument(kw):
+    assert call(**kw) == (_lib.ERR_NULL, WHO + "NULL pointer")
+
+
+@pytest.mark.parametrize("kw,rc,msg", [
+    (dict(gy=[FAKE, 0]), -1, "gy[1] is NULL"),
+    (dict(gy=[0, 0]), -1, "gy[0] is NULL"),
+    (dict(n_terms=0), -2, "n_terms=0, need 1..8"),
+    (dict(n_terms=9, gy=[FAKE] * 9, oH=[4] * 9, oW=[4] * 9), -2, "n_terms=9, need 1..8"),
+    (dict(n_terms=-1), -2, "n_terms=-1, need 1..8"),
+    (dict(Cc=0), -2, "bad shape N=1 C=0 H=8 W=8"),
+    (dict(H=0), -2, "bad shape N=1 C=3 H=0 W=8"),
+    (dict(W=0), -2, "bad shape N=1 C=3 H=8 W=0"),
+    (dict(N=-1), -2, "bad shape N=-1 C=3 H=8 W=8"),
+    (dict(oH=(4, 0)), -2, "term 1 is empty (oH=0 oW=2)"),
+    (dict(oW=(0, 2)), -2, "term 0 is empty (oH=4 oW=0)"),
+    (dict(oH=(-3, 2)), -2, "term 0 is empty (oH=-3 oW=4)"),
+    (dict(N=1 << 20, Cc=1 << 10, H=1 << 10, W=1, oH=(1,), oW=(1,)), -2, "too large"),            # N C H W = 2^40
+    (dict(N=1 << 20, Cc=1 << 10, H=1, W=1, oH=(1 << 10,), oW=(1,)), -2, "too large"),            # the elements of gy
+    # two faults at once: which check fires first
+    (dict(gx=None, n_terms=9), -1, "NULL pointer"),
+    (dict(gx=None, N=-1), -1, "NULL pointer"),
+    (dict(n_terms=9, Cc=0), -2, "n_terms=9, need 1..8"),
+    (dict(Cc=0, oH=(0, 2)), -2, "bad shape N=1 C=0 H=8 W=8"),
+    (dict(gy=[0, FAKE], oH=(0, 2)), -2, "term 0 is empty (oH=0 oW=4)"),
+    (dict(gy=[FAKE, 0], oH=(4, 2, 0), oW=(4, 2, 1)), -1, "gy[1] is NULL"),
+    (dict(gy=[FAKE, 0], N=1 << 20, Cc=1 << 10, H=1 << 10, W=1), -1, "gy[1] is NULL"),
+])
+def test_rejected_calls(kw, rc, msg):
+    assert call(**kw) == (rc, WHO + msg)
+
+
+@pytest.mark.parametrize("kw", [dict(N=0), dict(N=0, gy=[0, 0]), dict(N=0, gx=None), dict(N=0, gy=[0, 0], gx=None, Cc=65536)])
+def test_an_empty_batch_is_accepted_before_any_launch(kw):
+    """N = 0 returns 0, launches nothing and leaves sfm_last_error() as it was"""
+    assert call(**kw) == (0, None)
+
+
+def test_an_empty_batch_is_still_validated():
+    assert call(N=0, Cc=0) == (-2, WHO + "bad shape N=0 C=0 H=8 W=8")
+    assert call(N=0, oH=(0, 2)) == (-2, WHO + "term 0 is empty (oH=0 oW=4)")
+    assert call(N=0, gy=None) == (-1, WHO + "NULL pointer")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# host layer
+# ------------------------------------------------------------------------------------------------------------------------
+class _OnDevice(torch.Tensor):
+    """A host tensor that says it lives on a device: enough for the checks that come before the launch (none is reached)."""
+    is_cuda = True
+
+
+def test_ops_resize_bwd_rejects_before_the_library():
+    assert "resize_bwd" in ops.__all__
+    g = torch.zeros((2, 3, 4, 5), dtype=torch.float32)
+    with pytest.raises(TypeError, match="CPU arrays are not supported"):
+        ops.resize_bwd(g, (8, 10))
+    with pytest.raises(TypeError, match="CPU arrays are not supported"):
+        ops.resize_bwd([g], (8, 10))
+    with pytest.raises(TypeError, match="expected a torch.Tensor"):
+        ops.resize_bwd([g.numpy()], (8, 10))
+    with pytest.raises(TypeError, match="1..8 gradient arrays, got 0"):
+        ops.resize_bwd([], (8, 10))
+    with pytest.raises(TypeError, match="1..8 gradient arrays, got 9"):
+        ops.resize_bwd([g] * 9, (8, 10))
+    dev = lambda t: t.as_subclass(_OnDevice)
+    with pytest.raises(TypeError, match="expected dtype float32"):
+        ops.resize_bwd(dev(g.double()), (8, 10))
+    with pytest.raises(TypeError, match="expected ndim == 4, got 3"):
+        ops.resize_bwd(dev(g[0]), (8, 10))
+    with pytest.raises(TypeError, match=r"gys\[1\].*N, C and the device must agree"):
+        ops.resize_bwd([dev(g), dev(torch.zeros((1, 3, 2, 2)))], (8, 10))
+    with pytest.raises(TypeError, match=r"gys\[1\].*N, C and the device must agree"):
+        ops.resize_bwd([dev(g), dev(torch.zeros((2, 4, 2, 2)))], (8, 10))
+
+
+def test_resize_images_of_a_constant_is_a_constant(monkeypatch):
+    """functions.resize_images on an array or a Variable that requires no gradient: requires_grad=False and no graph, as before"""
+    monkeypatch.setattr(ops, "resize", lambda x, out_hw: torch.zeros(tuple(x.shape[:2]) + tuple(out_hw)))
+    x = torch.zeros((1, 2, 4, 6)).as_subclass(_OnDevice)
+    for arg in (x, surface.Variable(x, requires_grad=False)):
+        y = functions.resize_images(arg, (2, 3))
+        assert isinstance(y, surface.Variable) and y.shape == (1, 2, 2, 3)
+        assert y.requires_grad is False and y.creator is None
+    y = functions.resize_images(surface.Variable(x), (2, 3))
+    assert y.requires_grad and isinstance(y.creator, functions.ResizeImages)
+    with pytest.raises(TypeError):
+        functions.resize_images(x.double(), (2, 3))
+    with pytest.raises(TypeError):
+        functions.resize_images(x[0], (2, 3))
+
+
+def test_torch_api_names():
+    ta = importlib.import_module("sfm-learner-chainer_amd.torch_api")
+    assert {"resize_images", "resize_like"} <= set(ta.__all__)
+    a = torch.zeros((1, 2, 4, 6))
+    assert ta.resize_like(a, torch.zeros((3, 5, 4, 6))) is a          # the reference's short-circuit (models/disp_net.py:11-14)
+    with pytest.raises(TypeError, match="CPU arrays are not supported"):
+        ta.resize_images(a, (2, 3))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the emulation of the kernel's arithmetic against the fp64 reference
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,out", R.EXACT_CASES)
+def test_the_emulation_is_exact_where_the_weights_are_dyadic(shape, out):
+    gy = R.exact_gy(shape, out)
+    want = R.ref64(gy, shape[2:])
+    np.testing.assert_array_equal(R.emulate([gy], shape[2:]).astype(np.float64), want)
+    if tuple(shape[2:]) == tuple(out):
+        np.testing.assert_array_equal(want, gy)
+    if (shape[2:], out) == ((9, 13), (5, 7)):          # a pure pick: zeros at the odd positions
+        assert not want[:, :, 1::2].any() and not want[:, :, :, 1::2].any()
+        np.testing.assert_array_equal(want[:, :, ::2, ::2], gy)
+
+
+@pytest.mark.parametrize("shape,out", [c for c in R.EDGE_CASES if c[0][1] < 1000 and c[1] != (128, 416)])
+def test_the_emulation_is_within_the_derived_tolerance(shape, out):
+    """so the fp64 reference alone lies inside the tolerance the GPU test applies (the two largest cases are left to the GPU)"""
+    gy = R.edge_gy(shape, out)
+    err = np.abs(R.emulate([gy], shape[2:]) - R.ref64(gy, shape[2:])).max()
+    assert err <= R.tol(gy, shape[2:]), (err, R.tol(gy, shape[2:]))
+
+
+def test_touch_counts():
+    """counted from the tap INDICES, a tap of weight 0 included (the same size: o - 1 through its tap1, o, and the clamped last)"""
+    assert R.touch_count(8, 8) == 3 and R.touch_count(1, 5) == 5 and R.touch_count(2, 7) == 7
+    assert R.touch_count(9, 5) == 2 and R.touch_count(37, 18) == 1      # steps of 2 and more: the outputs' taps do not overlap
+    assert R.touch_count(5, 9) == 5 and R.touch_count(8, 128) == 37     # upsampling by r: about 2 r + 1
