@@ -1,4 +1,4 @@
-"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h).  No torch types cross this boundary:
+"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h, include/sfmwarp_intrinsics.h).  No torch types cross this boundary:
 every tensor is handed over as a raw device pointer plus explicit sizes.
 
 The library is REQUIRED: there is no CPU or PyTorch fallback.  If it is missing, importing
@@ -109,6 +109,15 @@ EXT_SYMBOLS = {
 }
 
 
+# every symbol declared in include/sfmwarp_intrinsics.h (the gradient with respect to the camera intrinsics)
+INTRINSICS_SYMBOLS = {
+    "sfm_loss_proj_bwd": (_I, [C.POINTER(SfmLossDesc), _I, _V, _Z, _FP, _FP, _V]),
+    "sfm_warp_intrinsics_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
+    "sfm_warp_intrinsics_bwd": (_I, [_FP, _FP, _I, _FP, _FP, _FP, _FP, _V, _Z, _I, _I, _I, _I, _V]),
+    "sfm_pose_proj_bwd_k": (_I, [_FP, _FP, _FP, _FP, _I, _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -119,7 +128,7 @@ def _load():
             "libsfmwarp.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(INTRINSICS_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

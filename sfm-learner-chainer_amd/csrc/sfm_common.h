@@ -168,6 +168,66 @@ __device__ __forceinline__ void pose_backward(const float* pose6, const float* g
 }
 
 // ------------------------------------------------------------------------------------------
+// The gradient with respect to the intrinsics, in fp64 (one lane per matrix: a few hundred operations behind sums that were
+// reduced in fp64 already; rounded once, by the caller).  With Pm = K [R|t] (transform.py:86-88) and ray = K^-1 pix (:105):
+//   dL/dK = gPm[0:3, :] [R|t]^T  -  K^-T gKinv-path,   gKinv = dL/d(K^-1)   =>   - K^-T gKinv K^-T   (F.batch_inv backward)
+// ------------------------------------------------------------------------------------------
+// euler2mat / pose_vec2mat (transform.py:11-59) in fp64: R (3x3, row-major) = (X . Y) . Z of the clipped angles, t
+__device__ __forceinline__ void pose_rt_d(const float* pose6, double* R, double* t) {
+  const double pi = (double)3.14159265358979323846f;     // (the reference clips float32 angles to float32 pi)
+  double s[3], c[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double a = fmin(fmax((double)pose6[k], -pi), pi);
+    s[k] = sin(a);
+    c[k] = cos(a);
+    t[k] = (double)pose6[3 + k];
+  }
+  const double sx = s[0], cx = c[0], sy = s[1], cy = c[1], sz = s[2], cz = c[2];
+  // X Y = [[cy, 0, sy], [sx sy, cx, -sx cy], [-cx sy, sx, cx cy]] ;  (M Z) columns = [M0 cz + M1 sz, -M0 sz + M1 cz, M2]
+  const double XY[9] = {cy, 0.0, sy, sx * sy, cx, -sx * cy, -cx * sy, sx, cx * cy};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    R[r * 3 + 0] = XY[r * 3 + 0] * cz + XY[r * 3 + 1] * sz;
+    R[r * 3 + 1] = -XY[r * 3 + 0] * sz + XY[r * 3 + 1] * cz;
+    R[r * 3 + 2] = XY[r * 3 + 2];
+  }
+}
+
+// batch_inv (transform.py:105) in fp64: adjugate / determinant
+__device__ __forceinline__ void inv3_d(const double* K, double* o) {
+  const double a = K[0], b = K[1], c = K[2], d = K[3], e = K[4], f = K[5], g = K[6], h = K[7], i = K[8];
+  const double A = e * i - f * h, B = f * g - d * i, C = d * h - e * g;
+  const double r = 1.0 / (a * A + b * B + c * C);
+  o[0] = A * r; o[1] = (c * h - b * i) * r; o[2] = (b * f - c * e) * r;
+  o[3] = B * r; o[4] = (a * i - c * g) * r; o[5] = (c * d - a * f) * r;
+  o[6] = C * r; o[7] = (b * g - a * h) * r; o[8] = (a * e - b * d) * r;
+}
+
+// dK (3x3) += gPm[0:3, :] . [R|t]^T   (gPm: 3x4 row-major; the proj_tgt_to_src route, transform.py:86-88)
+__device__ __forceinline__ void dk_from_gpm_d(const double* gPm, const double* R, const double* t, double* dK) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      dK[k * 3 + c] += gPm[k * 4 + 0] * R[c * 3 + 0] + gPm[k * 4 + 1] * R[c * 3 + 1] + gPm[k * 4 + 2] * R[c * 3 + 2] + gPm[k * 4 + 3] * t[c];
+}
+
+// o (3x3) = a^T . b
+__device__ __forceinline__ void mat3_mul_tn_d(const double* a, const double* b, double* o) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[i * 3 + j] = a[0 * 3 + i] * b[0 * 3 + j] + a[1 * 3 + i] * b[1 * 3 + j] + a[2 * 3 + i] * b[2 * 3 + j];
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {   // xor butterfly: a fixed order, the same bits in every lane
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ------------------------------------------------------------------------------------------
 // wave-level helpers (wave = 64 lanes)
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }

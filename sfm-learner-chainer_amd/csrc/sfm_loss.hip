@@ -24,6 +24,7 @@
 #include <hip/hip_ext.h>
 
 #include "sfm_loss_kernels.h"
+#include "sfmwarp_intrinsics.h"
 
 namespace sfm {
 
@@ -32,12 +33,6 @@ namespace sfm {
 //   blocks [0, B*n_src): d_pose of (b, i)         (only when do_pose)
 //   last block        : the five reported scalars (only when loss5 != nullptr)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 #ifdef SFM_FIN_STAMPS   // diagnostic build only: 100 MHz time stamps of finalize_kernel's stages into the debug trace buffer (tools/trace_finalize.py)
 #define SFM_FSTAMP(slot) do { if (A.trace && threadIdx.x == 0) A.trace[200000 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define SFM_FSTAMP_F(slot) do { if (A.trace && threadIdx.x == 64) A.trace[200000 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)   // first FOLDING wave
@@ -309,6 +304,83 @@ __global__ void __launch_bounds__(64 * FINALIZE_WAVES) finalize_kernel(const flo
     loss5[3] = (float)expl;
     loss5[4] = (float)ssim;
     SFM_FSTAMP(11);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// sfm_loss_proj_bwd: dL/dPm and dL/d(intrinsics) from the raw pose sums a gradient launch has left in part_gpm
+//   block = (sample b, scale s), wave i = source i: every lane adds its tiles t = lane, lane + 64, ... in ascending order in fp64,
+//   the 64 lane sums meet in an xor butterfly (a fixed order), lane 0 forms K^-1 and the products in fp64:
+//     gPm[:, 0:3] = S . K^-T , gPm[:, 3] = s3           (pose_sums_raw; what finalize_kernel forms per tile in fp32)
+//     dK_i = gPm[:, 0:3] . R^T + gPm[:, 3] . t^T - K^-T . R^T . K^T . gPm[:, 0:3]      (transform.py:86-88 and, via F.batch_inv, :105)
+//   and the sources' dK_i are added in source order.  Reads the workspace, writes only its two outputs.
+// ------------------------------------------------------------------------------------------
+struct ProjBwdArgs {
+  const float* part_gpm;
+  const float* intrinsics;
+  const float* pose[SFM_MAX_SRC];
+  float* d_proj;   // (B, n_scales, n_src, 3, 4) or nullptr
+  float* d_intr;   // (B, n_scales, 3, 3) or nullptr
+  int B, n_src, n_scales;
+  int tiles_of[SFM_MAX_SCALES], item_begin_of[SFM_MAX_SCALES];
+};
+
+__global__ void __launch_bounds__(64 * SFM_MAX_SRC) proj_bwd_kernel(const ProjBwdArgs A) {
+  __shared__ double dk_of[SFM_MAX_SRC][9];
+  const int lane = threadIdx.x & 63, i = threadIdx.x >> 6;      // blockDim.x = 64 * n_src
+  const int b = blockIdx.x / A.n_scales, s = blockIdx.x - b * A.n_scales;
+  const int tiles = A.tiles_of[s];
+  const size_t first = (size_t)A.item_begin_of[s] + (size_t)b * tiles;
+  double acc[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) acc[k] = 0.0;
+  for (int t = lane; t < tiles; t += 64) {
+    const float4* p = reinterpret_cast<const float4*>(A.part_gpm + ((first + t) * A.n_src + i) * 12);
+    const float4 v0 = p[0], v1 = p[1], v2 = p[2];
+    acc[0] += (double)v0.x; acc[1] += (double)v0.y; acc[2] += (double)v0.z; acc[3] += (double)v0.w;
+    acc[4] += (double)v1.x; acc[5] += (double)v1.y; acc[6] += (double)v1.z; acc[7] += (double)v1.w;
+    acc[8] += (double)v2.x; acc[9] += (double)v2.y; acc[10] += (double)v2.z; acc[11] += (double)v2.w;
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) acc[k] = wave_sum_d(acc[k]);
+  if (lane == 0) {
+    const float* Kp = A.intrinsics + ((size_t)b * A.n_scales + s) * 9;
+    double K[9], Ki[9], R[9], t[3], gPm[12];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) K[k] = (double)Kp[k];
+    inv3_d(K, Ki);
+    const float* pp = A.pose[0];      // (selected, not indexed: the argument block stays in scalar registers)
+#pragma unroll
+    for (int k = 1; k < SFM_MAX_SRC; ++k) pp = (i == k) ? A.pose[k] : pp;
+    pose_rt_d(pp + (size_t)b * 6, R, t);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) gPm[k * 4 + j] = Ki[j * 3 + 0] * acc[k * 4 + 0] + Ki[j * 3 + 1] * acc[k * 4 + 1] + Ki[j * 3 + 2] * acc[k * 4 + 2];
+      gPm[k * 4 + 3] = acc[k * 4 + 3];
+    }
+    if (A.d_proj) {
+      float* o = A.d_proj + (((size_t)b * A.n_scales + s) * A.n_src + i) * 12;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) o[k] = (float)gPm[k];
+    }
+    double g3[9], m1[9], m2[9], m3[9], dK[9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { g3[k * 3 + j] = gPm[k * 4 + j]; dK[k * 3 + j] = 0.0; }
+    dk_from_gpm_d(gPm, R, t, dK);
+    mat3_mul_tn_d(K, g3, m1);      // K^T . gPm3
+    mat3_mul_tn_d(R, m1, m2);      // R^T . K^T . gPm3
+    mat3_mul_tn_d(Ki, m2, m3);     // K^-T . R^T . K^T . gPm3
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dk_of[i][k] = dK[k] - m3[k];
+  }
+  __syncthreads();
+  if (A.d_intr && threadIdx.x < 9) {
+    double a = dk_of[0][threadIdx.x];
+    for (int k = 1; k < A.n_src; ++k) a += dk_of[k][threadIdx.x];
+    A.d_intr[((size_t)b * A.n_scales + s) * 9 + threadIdx.x] = (float)a;
   }
 }
 
@@ -946,6 +1018,33 @@ int sfm_loss_bwd(const SfmLossDesc* desc, float gy, void* ws, size_t ws_bytes, v
 
 int sfm_loss_fwd_bwd(const SfmLossDesc* desc, float* loss5, void* ws, size_t ws_bytes, void* stream) {
   return sfm::run(desc, sfm::ENTRY_FWD_BWD, 1.f, loss5, ws, ws_bytes, stream, "sfm_loss_fwd_bwd", nullptr);
+}
+
+int sfm_loss_proj_bwd(const SfmLossDesc* desc, int loss, const void* ws, size_t ws_bytes, float* d_proj, float* d_intrinsics,
+                      void* stream) {
+  const char* who = "sfm_loss_proj_bwd";
+  if (!desc) return sfm::fail(SFM_ERR_NULL, "%s: NULL descriptor", who);
+  if (desc->B == 0) {      // empty shard: nothing to launch (input pointers of empty arrays may be NULL, as for sfm_loss_bwd)
+    if (!d_proj && !d_intrinsics) return sfm::fail(SFM_ERR_NULL, "%s: d_proj and d_intrinsics are both NULL", who);
+    return SFM_OK;
+  }
+  // the plan of the gradient call whose sums lie in `ws` (found in the thread's plan cache when that call has just been made):
+  // the library's own choice of kernel, no one-call hook
+  sfm::Plan p;
+  if (int err = sfm::cached_plan(desc, loss ? sfm::ENTRY_FWD_BWD : sfm::ENTRY_BWD, 1.f, p, -1)) return err;
+  if (!d_proj && !d_intrinsics) return sfm::fail(SFM_ERR_NULL, "%s: d_proj and d_intrinsics are both NULL", who);
+  if (!ws || ws_bytes < p.total) return sfm::fail(SFM_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, got %zu", who, p.total, ws_bytes);
+  if (((uintptr_t)ws & 255) != 0) return sfm::fail(SFM_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+  sfm::ProjBwdArgs A = {};
+  A.part_gpm = (const float*)((const char*)ws + p.off_gpm);
+  A.intrinsics = desc->intrinsics;
+  for (int i = 0; i < desc->n_src; ++i) A.pose[i] = desc->pose[i];
+  A.d_proj = d_proj;
+  A.d_intr = d_intrinsics;
+  A.B = desc->B; A.n_src = desc->n_src; A.n_scales = desc->n_scales;
+  for (int s = 0; s < SFM_MAX_SCALES; ++s) { A.tiles_of[s] = p.args.tiles_of[s]; A.item_begin_of[s] = p.args.item_begin_of[s]; }
+  hipLaunchKernelGGL(sfm::proj_bwd_kernel, dim3(desc->B * desc->n_scales), dim3(64 * desc->n_src), 0, (hipStream_t)stream, A);
+  return sfm::check_launch(who);
 }
 
 // One step of SFMLearner.__call__ from the full-resolution frames (models/base_model.py:48-124) in ONE call: the loop head :69-72 --

@@ -7,6 +7,7 @@
 
 #include "sfm_common.h"
 #include "sfmwarp_ext.h"
+#include "sfmwarp_intrinsics.h"
 
 #define SFM_REQUIRE(cond, code, ...) \
   do {                               \
@@ -198,8 +199,55 @@ __global__ void __launch_bounds__(WARP_BLOCK) warp_fwd_kernel(const float* __res
   }
 }
 
-// per pixel: the reference's backward chain (sampler -> x mask -> normalisation -> perspective division -> Pm . c4 -> D (.) ray),
-// d_depth, and the 12 sums of gPm (block-reduced into ws)
+// per pixel: the reference's backward chain sampler -> x mask -> normalisation -> perspective division, i.e. dL/dq of q = Pm . c4
+// (transform.py:122-131,189 backward), and the sampler's scatter into d_src when that is bound.  ONE function for sfm_warp_bwd and
+// sfm_warp_intrinsics_bwd: the two differentiate the same dL/dq.
+struct WarpGq {
+  RefProj r;
+  float gq[3];
+};
+
+__device__ __forceinline__ WarpGq warp_pixel_gq(const Geom& g, const float* __restrict__ src, const float* __restrict__ depth,
+                                                const float* __restrict__ g_warped, float* __restrict__ d_src, const int n, const int C,
+                                                const int H, const int W, const int drows, const int j) {
+#pragma clang fp contract(off)
+  WarpGq o;
+  const int P = H * W;
+  const int y = j / W, x = j - y * W;
+  float D[3];
+  load_depth3(depth, n, drows, P, j, D);
+  o.r = ref_project(g, (float)x, (float)y, D, H, W);
+  const RefProj& r = o.r;
+  const PadTap t = pad_taps(r.gx, r.gy, H, W);
+  float gu = 0.f, gv = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float* img = src + ((size_t)n * C + c) * P;
+    const float gc = g_warped[((size_t)n * C + c) * P + j];
+    const float x1 = pad_read(img, t.v0, t.u0, H, W), x2 = pad_read(img, t.v0, t.u0 + 1, H, W);
+    const float x3 = pad_read(img, t.v0 + 1, t.u0, H, W), x4 = pad_read(img, t.v0 + 1, t.u0 + 1, H, W);
+    gu += gc * (-t.wy0 * x1 + t.wy0 * x2 - t.wy1 * x3 + t.wy1 * x4);
+    gv += gc * (-t.wx0 * x1 - t.wx1 * x2 + t.wx0 * x3 + t.wx1 * x4);
+    if (d_src) {
+      float* dst = d_src + ((size_t)n * C + c) * P;
+      const int u = t.u0, v = t.v0;   // padded coordinates: taps on the zero frame receive nothing
+      if (u >= 1 && u <= W && v >= 1 && v <= H) atomicAdd(dst + (v - 1) * W + (u - 1), gc * t.wx0 * t.wy0);
+      if (u + 1 >= 1 && u + 1 <= W && v >= 1 && v <= H) atomicAdd(dst + (v - 1) * W + u, gc * t.wx1 * t.wy0);
+      if (u >= 1 && u <= W && v + 1 >= 1 && v + 1 <= H) atomicAdd(dst + v * W + (u - 1), gc * t.wx0 * t.wy1);
+      if (u + 1 >= 1 && u + 1 <= W && v + 1 >= 1 && v + 1 <= H) atomicAdd(dst + v * W + u, gc * t.wx1 * t.wy1);
+    }
+  }
+  // sampler backward to the grid, then p_s_xy *= mask (transform.py:131)
+  const float ggx = t.ok_u ? gu * ((float)(W - 1) * 0.5f) : 0.f;
+  const float ggy = t.ok_v ? gv * ((float)(H - 1) * 0.5f) : 0.f;
+  const float half_w = (float)((double)(W - 1) / 2.0), half_h = (float)((double)(H - 1) / 2.0);
+  const float gU = (ggx * r.mx) / half_w, gV = (ggy * r.my) / half_h;
+  o.gq[0] = gU / r.z;
+  o.gq[1] = gV / r.z;
+  o.gq[2] = -(gU * r.U + gV * r.V) / r.z;
+  return o;
+}
+
+// per pixel: dL/dq (warp_pixel_gq), d_depth, and the 12 sums of gPm (block-reduced into ws)
 __global__ void __launch_bounds__(WARP_BLOCK) warp_bwd_kernel(const float* __restrict__ src, const float* __restrict__ depth,
                                                               const float* __restrict__ pose6, const float* __restrict__ K,
                                                               const float* __restrict__ g_warped, float* __restrict__ d_depth,
@@ -217,35 +265,9 @@ __global__ void __launch_bounds__(WARP_BLOCK) warp_bwd_kernel(const float* __res
 #pragma unroll
   for (int k = 0; k < 12; ++k) acc[k] = 0.f;
   if (j < P) {
-    const int y = j / W, x = j - y * W;
-    float D[3];
-    load_depth3(depth, n, drows, P, j, D);
-    const RefProj r = ref_project(g, (float)x, (float)y, D, H, W);
-    const PadTap t = pad_taps(r.gx, r.gy, H, W);
-    float gu = 0.f, gv = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float* img = src + ((size_t)n * C + c) * P;
-      const float gc = g_warped[((size_t)n * C + c) * P + j];
-      const float x1 = pad_read(img, t.v0, t.u0, H, W), x2 = pad_read(img, t.v0, t.u0 + 1, H, W);
-      const float x3 = pad_read(img, t.v0 + 1, t.u0, H, W), x4 = pad_read(img, t.v0 + 1, t.u0 + 1, H, W);
-      gu += gc * (-t.wy0 * x1 + t.wy0 * x2 - t.wy1 * x3 + t.wy1 * x4);
-      gv += gc * (-t.wx0 * x1 - t.wx1 * x2 + t.wx0 * x3 + t.wx1 * x4);
-      if (d_src) {
-        float* o = d_src + ((size_t)n * C + c) * P;
-        const int u = t.u0, v = t.v0;   // padded coordinates: taps on the zero frame receive nothing
-        if (u >= 1 && u <= W && v >= 1 && v <= H) atomicAdd(o + (v - 1) * W + (u - 1), gc * t.wx0 * t.wy0);
-        if (u + 1 >= 1 && u + 1 <= W && v >= 1 && v <= H) atomicAdd(o + (v - 1) * W + u, gc * t.wx1 * t.wy0);
-        if (u >= 1 && u <= W && v + 1 >= 1 && v + 1 <= H) atomicAdd(o + v * W + (u - 1), gc * t.wx0 * t.wy1);
-        if (u + 1 >= 1 && u + 1 <= W && v + 1 >= 1 && v + 1 <= H) atomicAdd(o + v * W + u, gc * t.wx1 * t.wy1);
-      }
-    }
-    // sampler backward to the grid, then p_s_xy *= mask (transform.py:131)
-    const float ggx = t.ok_u ? gu * ((float)(W - 1) * 0.5f) : 0.f;
-    const float ggy = t.ok_v ? gv * ((float)(H - 1) * 0.5f) : 0.f;
-    const float half_w = (float)((double)(W - 1) / 2.0), half_h = (float)((double)(H - 1) / 2.0);
-    const float gU = (ggx * r.mx) / half_w, gV = (ggy * r.my) / half_h;
-    const float gq0 = gU / r.z, gq1 = gV / r.z;
-    const float gq2 = -(gU * r.U + gV * r.V) / r.z;
+    const WarpGq w = warp_pixel_gq(g, src, depth, g_warped, d_src, n, C, H, W, drows, j);
+    const RefProj& r = w.r;
+    const float gq0 = w.gq[0], gq1 = w.gq[1], gq2 = w.gq[2];
     // g_c = Pm^T . gq ; g_depthes[j] = g_c[j] * ray[j]   (transform.py:107,122 backward)
     const float gd0 = ((g.P[0] * gq0 + g.P[4] * gq1) + g.P[8] * gq2) * r.ray[0];
     const float gd1 = ((g.P[1] * gq0 + g.P[5] * gq1) + g.P[9] * gq2) * r.ray[1];
@@ -274,6 +296,104 @@ __global__ void __launch_bounds__(WARP_BLOCK) warp_bwd_kernel(const float* __res
     for (int w = 0; w < WARP_BLOCK / 64; ++w) s += red[w][threadIdx.x];
     part[((size_t)n * gridDim.x + blockIdx.x) * 12 + threadIdx.x] = s;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// sfm_warp_intrinsics_bwd: dL/dK of projective_inverse_warp.  K enters Pm = K4 . [R|t] (transform.py:86-88) and, inverted, the rays
+// ray = K^-1 . pix (:105).  Per pixel, with dL/dq of warp_pixel_gq:
+//   gPm[k][:] += gq_k (c, 1)                                    (as warp_bwd_kernel; :122 backward)
+//   G[k][:]   += g_ray_k (x, y, 1),  g_ray_k = D_k (Pm^T gq)_k  (:105-107 backward; the three depth rows may differ)
+// 21 sums per block, reduced over the wave in lockstep and over the block's waves in wave order; intr_bwd_fold_kernel adds the
+// blocks of a sample in a fixed order in fp64 and finishes  d_K = gPm[0:3, :] [R|t]^T - K^-T G K^-T  (F.batch_inv backward).
+// ------------------------------------------------------------------------------------------
+constexpr int INTR_SUMS = 21;
+
+__global__ void __launch_bounds__(WARP_BLOCK) warp_intr_bwd_kernel(const float* __restrict__ src, const float* __restrict__ depth,
+                                                                   const float* __restrict__ pose6, const float* __restrict__ K,
+                                                                   const float* __restrict__ g_warped, float* __restrict__ part, int C,
+                                                                   int H, int W, int drows) {
+#pragma clang fp contract(off)
+  __shared__ Geom g;
+  __shared__ float red[WARP_BLOCK / 64][INTR_SUMS];
+  const int n = blockIdx.y;
+  if (threadIdx.x == 0) make_geom(pose6 + n * 6, K + n * 9, g);
+  __syncthreads();
+  const int P = H * W;
+  const int j = blockIdx.x * WARP_BLOCK + threadIdx.x;
+  float acc[INTR_SUMS];
+#pragma unroll
+  for (int k = 0; k < INTR_SUMS; ++k) acc[k] = 0.f;
+  if (j < P) {
+    const WarpGq w = warp_pixel_gq(g, src, depth, g_warped, nullptr, n, C, H, W, drows, j);
+    const RefProj& r = w.r;
+    const int y = j / W, x = j - y * W;
+    const float xf = (float)x, yf = (float)y;
+    float D[3];
+    load_depth3(depth, n, drows, P, j, D);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      acc[k * 4 + 0] = w.gq[k] * r.c[0]; acc[k * 4 + 1] = w.gq[k] * r.c[1]; acc[k * 4 + 2] = w.gq[k] * r.c[2]; acc[k * 4 + 3] = w.gq[k];
+      const float g_ray = D[k] * ((g.P[0 * 4 + k] * w.gq[0] + g.P[1 * 4 + k] * w.gq[1]) + g.P[2 * 4 + k] * w.gq[2]);
+      acc[12 + k * 3 + 0] = g_ray * xf; acc[12 + k * 3 + 1] = g_ray * yf; acc[12 + k * 3 + 2] = g_ray;
+    }
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  wave_sums_lockstep(acc);       // (lanes without a pixel contribute zeros)
+  if (lane == 63) {
+#pragma unroll
+    for (int k = 0; k < INTR_SUMS; ++k) red[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < INTR_SUMS) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < WARP_BLOCK / 64; ++w) s += red[w][threadIdx.x];
+    part[((size_t)n * gridDim.x + blockIdx.x) * INTR_SUMS + threadIdx.x] = s;
+  }
+}
+
+// one wave per sample: fixed-order sum of the block partials in fp64, then d_K
+__global__ void __launch_bounds__(64) intr_bwd_fold_kernel(const float* __restrict__ pose6, const float* __restrict__ K,
+                                                           const float* __restrict__ part, float* __restrict__ d_K, int nblk) {
+  const int n = blockIdx.x, lane = threadIdx.x;
+  double acc[INTR_SUMS];
+#pragma unroll
+  for (int k = 0; k < INTR_SUMS; ++k) acc[k] = 0.0;
+  for (int b = lane; b < nblk; b += 64)
+#pragma unroll
+    for (int k = 0; k < INTR_SUMS; ++k) acc[k] += (double)part[((size_t)n * nblk + b) * INTR_SUMS + k];
+#pragma unroll
+  for (int k = 0; k < INTR_SUMS; ++k) acc[k] = wave_sum_d(acc[k]);
+  if (lane == 0) {
+    double Kd[9], Ki[9], R[9], t[3], dK[9], m1[9], m2[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { Kd[k] = (double)K[n * 9 + k]; dK[k] = 0.0; }
+    inv3_d(Kd, Ki);
+    pose_rt_d(pose6 + n * 6, R, t);
+    dk_from_gpm_d(acc, R, t, dK);
+    mat3_mul_tn_d(Ki, acc + 12, m1);      // K^-T . G
+#pragma unroll
+    for (int i = 0; i < 3; ++i)           // (K^-T . G) . K^-T
+#pragma unroll
+      for (int c = 0; c < 3; ++c) m2[i * 3 + c] = m1[i * 3 + 0] * Ki[c * 3 + 0] + m1[i * 3 + 1] * Ki[c * 3 + 1] + m1[i * 3 + 2] * Ki[c * 3 + 2];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) d_K[n * 9 + k] = (float)(dK[k] - m2[k]);
+  }
+}
+
+// sfm_pose_proj_bwd_k: d_K = g_proj[0:3, :] . [R|t]^T   (transform.py:86-88)
+__global__ void pose_proj_bwd_k_kernel(const float* __restrict__ pose6, const float* __restrict__ g_proj, float* __restrict__ d_K, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  double R[9], t[3], gPm[12], dK[9];
+  pose_rt_d(pose6 + (size_t)n * 6, R, t);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) gPm[k] = (double)g_proj[(size_t)n * 16 + k];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) dK[k] = 0.0;
+  dk_from_gpm_d(gPm, R, t, dK);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) d_K[(size_t)n * 9 + k] = (float)dK[k];
 }
 
 // one wave per sample: fixed-order sum of the block partials, then the pose backward
@@ -1182,6 +1302,36 @@ int sfm_warp_bwd(const float* src, const float* depth, int depth_rows, const flo
                      d_depth, d_src, (float*)ws, C, H, W, depth_rows);
   hipLaunchKernelGGL(warp_bwd_pose_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, pose6, K, (const float*)ws, d_pose6, nblk);
   return check_launch("sfm_warp_bwd");
+}
+
+size_t sfm_warp_intrinsics_bwd_workspace_bytes(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t nblk = ((size_t)H * W + WARP_BLOCK - 1) / WARP_BLOCK;
+  return (size_t)N * nblk * INTR_SUMS * sizeof(float);
+}
+
+int sfm_warp_intrinsics_bwd(const float* src, const float* depth, int depth_rows, const float* pose6, const float* K,
+                            const float* g_warped, float* d_K, void* ws, size_t ws_bytes, int N, int C, int H, int W, void* stream) {
+  const char* who = "sfm_warp_intrinsics_bwd";
+  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
+  SFM_REQUIRE(src && depth && pose6 && K && g_warped && d_K, SFM_ERR_NULL, "%s: NULL pointer", who);
+  if (int e = check_warp_shape(who, N, C, H, W)) return e;
+  SFM_REQUIRE(depth_rows == 1 || depth_rows == 3, SFM_ERR_SHAPE, "%s: depth_rows=%d, must be 1 or 3", who, depth_rows);
+  SFM_REQUIRE(ws && ws_bytes >= sfm_warp_intrinsics_bwd_workspace_bytes(N, H, W), SFM_ERR_WORKSPACE,
+              "%s: workspace of %zu bytes needed, got %zu", who, sfm_warp_intrinsics_bwd_workspace_bytes(N, H, W), ws_bytes);
+  const int nblk = (H * W + WARP_BLOCK - 1) / WARP_BLOCK;
+  hipLaunchKernelGGL(warp_intr_bwd_kernel, dim3(nblk, N), dim3(WARP_BLOCK), 0, (hipStream_t)stream, src, depth, pose6, K, g_warped,
+                     (float*)ws, C, H, W, depth_rows);
+  hipLaunchKernelGGL(intr_bwd_fold_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, pose6, K, (const float*)ws, d_K, nblk);
+  return check_launch(who);
+}
+
+int sfm_pose_proj_bwd_k(const float* pose6, const float* K, const float* g_proj, float* d_K, int N, void* stream) {
+  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
+  SFM_REQUIRE(pose6 && K && g_proj && d_K, SFM_ERR_NULL, "sfm_pose_proj_bwd_k: NULL pointer");
+  SFM_REQUIRE(N >= 0, SFM_ERR_SHAPE, "sfm_pose_proj_bwd_k: N=%d", N);
+  hipLaunchKernelGGL(pose_proj_bwd_k_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, pose6, g_proj, d_K, N);
+  return check_launch("sfm_pose_proj_bwd_k");
 }
 
 static int check_sampler_shape(const char* who, int N, int C, int H, int W, int oH, int oW) {

@@ -88,9 +88,15 @@ def spatial_transformer_sampler(x, grid, **kwargs):
     return SpatialTransformerSampler()(x, grid)
 
 
+def _wants_grad(function, k):
+    """input k of the call arrived as a Variable that requires a gradient (the reference passes K as an array: no work then)"""
+    x = getattr(function, "_inputs", ())[k:k + 1]
+    return bool(x) and isinstance(x[0], Variable) and x[0].requires_grad
+
+
 class ProjTgtToSrc(Function):
     """(vec (N,6), K (N,3,3)) -> projection (N,4,4), kept on the device (the reference moves
-    both to the CPU and the result back, transform.py:76-80,89-90)."""
+    both to the CPU and the result back, transform.py:76-80,89-90).  K as a Variable receives its gradient."""
 
     def check_type_forward(self, in_types):
         type_check.expect(in_types.size() == 2, in_types[0].dtype.char == 'f', in_types[1].dtype.char == 'f',
@@ -103,7 +109,8 @@ class ProjTgtToSrc(Function):
 
     def backward_gpu(self, inputs, grad_outputs):
         vec, K = inputs
-        return ops.pose_proj_bwd(vec, K, grad_outputs[0]), None
+        d_K = ops.pose_proj_bwd_intrinsics(vec, K, grad_outputs[0]) if _wants_grad(self, 1) else None
+        return ops.pose_proj_bwd(vec, K, grad_outputs[0]), d_K
 
 
 def proj_tgt_to_src(vec, K, N=None, xp=None, use_cpu=True):
@@ -112,7 +119,8 @@ def proj_tgt_to_src(vec, K, N=None, xp=None, use_cpu=True):
 
 
 class ProjectiveInverseWarp(Function):
-    """inputs: imgs (N,3,H,W), depthes (N,3,H*W), poses (N,6), K (N,3,3) -> (N,3,H,W)."""
+    """inputs: imgs (N,3,H,W), depthes (N,3,H*W), poses (N,6), K (N,3,3) -> (N,3,H,W).  K as a Variable receives its gradient
+    (ops.warp_bwd_intrinsics)."""
 
     def check_type_forward(self, in_types):
         type_check.expect(in_types.size() == 4)
@@ -131,7 +139,8 @@ class ProjectiveInverseWarp(Function):
     def backward_gpu(self, inputs, grad_outputs):
         imgs, depthes, poses, K = inputs
         d_depth, d_pose, d_src = ops.warp_bwd(imgs, depthes, poses, K, grad_outputs[0], want_d_src=True)
-        return d_src, d_depth, d_pose, None
+        d_K = ops.warp_bwd_intrinsics(imgs, depthes, poses, K, grad_outputs[0]) if _wants_grad(self, 3) else None
+        return d_src, d_depth, d_pose, d_K
 
 
 def projective_inverse_warp(imgs, depthes, poses, K):

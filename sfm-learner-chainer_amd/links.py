@@ -26,8 +26,9 @@ class _FusedLossFunction(Function):
     With backprop enabled the forward launch already produces every gradient
     (sfm_loss_fwd_bwd); backward only hands them out, scaled by the upstream gradient."""
 
-    def __init__(self, fused, S, n, with_masks, need_grad, run=None, state=None, frames=None):
+    def __init__(self, fused, S, n, with_masks, need_grad, run=None, state=None, frames=None, with_k=False):
         self.fused, self.S, self.n, self.with_masks, self.need_grad, self.run = fused, S, n, with_masks, need_grad, run
+        self.with_k = with_k       # the LAST input is the intrinsics, a Variable that receives fused.d_intrinsics
         # (tgt, stacked sources) at full resolution: pyramids + loss in ONE call through the C ABI (sfm_step_fwd_bwd); None: the
         # pyramids of this call have been built already (planar layout, HIP-graph replay)
         self.frames = frames
@@ -59,7 +60,7 @@ class _FusedLossFunction(Function):
         # any gradient the caller has set on the loss (e.g. a loss scale) is
         unit = getattr(self._outputs[0], "_unit_grad", False)
         f = self.fused
-        grads = list(f.d_disps) + list(f.d_poses) + (list(f.d_masks) if self.with_masks else [])
+        grads = list(f.d_disps) + list(f.d_poses) + (list(f.d_masks) if self.with_masks else []) + ([f.d_intrinsics] if self.with_k else [])
         return tuple(g if unit else g * gy for g in grads)
 
 
@@ -71,7 +72,7 @@ class _Cached:
 class _Repeat:
     """The arguments of the link's previous call, for the fast path of `SFMLearnerLoss.__call__`: a call that passes the very same
     objects, holding the very same arrays at the same addresses, has nothing to validate, reshape or re-bind."""
-    __slots__ = ("objs", "tensors", "ptrs", "st", "tgt", "stacked", "n_scales", "n_sources", "norm_batch")
+    __slots__ = ("objs", "tensors", "ptrs", "st", "tgt", "stacked", "n_scales", "n_sources", "norm_batch", "k_grad")
 
 
 _REPORTED = ("total_loss", "pixel_loss", "smooth_loss", "exp_loss", "ssim_loss")     # models/base_model.py:119-123, in loss5's order
@@ -128,10 +129,11 @@ class SFMLearnerLoss:
         self._cache = {}
         self._repeat = None
 
-    def _state(self, tgt, stacked, intrinsics, disps, poses, masks, norm_batch):
-        """The bound FusedLoss + pyramid buffers for these shapes (built on first use)."""
+    def _state(self, tgt, stacked, intrinsics, disps, poses, masks, norm_batch, k_grad=False):
+        """The bound FusedLoss + pyramid buffers for these shapes (built on first use).  k_grad: its gradient calls also leave
+        d_intrinsics (one more small launch, sfm_loss_proj_bwd)."""
         key = (tgt.device, tuple(tgt.shape), tuple(stacked.shape), tuple(intrinsics.shape), tuple(tuple(a.shape) for a in disps),
-               masks is not None, norm_batch)
+               masks is not None, norm_batch, k_grad)
         st = self._cache.get(key) if self.cache_buffers else None
         if st is None:
             st = _Cached()
@@ -140,7 +142,8 @@ class SFMLearnerLoss:
             _build_pyramids(st, tgt, stacked, len(disps))
             st.fused = ops.FusedLoss(smooth_reg=self.smooth_reg or 0.0, exp_reg=self.exp_reg or 0.0,
                                      ssim_rate=self.ssim_rate or 0.0, smooth_mode=self.smooth_mode, projection=self.projection)
-            st.fused.bind(st.pyr[0], st.pyr[1], intrinsics, disps, poses, masks, norm_B=norm_batch, layout=st.layout)
+            st.fused.bind(st.pyr[0], st.pyr[1], intrinsics, disps, poses, masks, norm_B=norm_batch, layout=st.layout,
+                          want_d_intrinsics=k_grad)
             st.graph = st.graph_key = st.graph_stream = None
             st.calls = 0
             if self.cache_buffers:
@@ -156,7 +159,8 @@ class SFMLearnerLoss:
            Args:
                tgt_img: target image. Shape is (Batch, 3, H, W)
                src_imgs: source images. Shape is (Batch, ?, 3, H, W)
-               intrinsics: Shape is (Batch, ?, 3, 3)
+               intrinsics: Shape is (Batch, ?, 3, 3).  An array, as in the reference; a Variable that requires a gradient (a learned
+                   calibration) has its `.grad` filled by `loss.backward()` along with the predictions'
                inv_intrinsics: unused, as in the reference (base_model.py:48)
                pred_disps: list of Variable (Batch, 1, H>>s, W>>s)   -- DispNet output (:59)
                pred_poses: list of Variable (Batch, 6)               -- PoseNet output (:62)
@@ -174,17 +178,20 @@ class SFMLearnerLoss:
             objs += pred_maskes
         inputs = objs[3:]
         need_grad = config.enable_backprop and any(isinstance(v, Variable) and v.requires_grad for v in inputs)
+        k_grad = type(intrinsics) is Variable and intrinsics.requires_grad
+        if k_grad and need_grad:
+            inputs = inputs + [intrinsics]         # the node's last input: it receives d_intrinsics
         # Fast path (round 6; the reference trains at B = 4, where a step is 25 us of GPU work and the host side of this call decides
         # the step time): the previous call's objects again, holding the same arrays at the same addresses -- static input buffers --
         # are neither validated nor re-bound a second time.
         rp = self._repeat
-        if rp is not None and norm_batch == rp.norm_batch and len(objs) == len(rp.objs):
+        if rp is not None and norm_batch == rp.norm_batch and len(objs) == len(rp.objs) and k_grad == rp.k_grad:
             for a, b, t, p in zip(objs, rp.objs, rp.tensors, rp.ptrs):
                 d = a.data if type(a) is Variable else a
                 if a is not b or d is not t or d.data_ptr() != p:
                     break
             else:
-                return self._finish(rp.st, inputs, rp.n_scales, rp.n_sources, do_exp, need_grad, None, (rp.tgt, rp.stacked))
+                return self._finish(rp.st, inputs, rp.n_scales, rp.n_sources, do_exp, need_grad, None, (rp.tgt, rp.stacked), k_grad)
         tgt = ops._dev(as_array(tgt_img), "tgt_img", 4)
         src = as_array(src_imgs)
         batchsize, n_sources, _, H, W = src.shape                              # :57
@@ -196,7 +203,7 @@ class SFMLearnerLoss:
         disps = [as_array(d) for d in pred_disps]
         poses = [as_array(p) for p in pred_poses]
         masks = [as_array(m) for m in pred_maskes] if do_exp else None
-        st, fresh = self._state(tgt, stacked_src_imgs, K, disps, poses, masks, norm_batch)
+        st, fresh = self._state(tgt, stacked_src_imgs, K, disps, poses, masks, norm_batch, k_grad)
         run = None
         if self.use_graph and self.cache_buffers:
             run = self._graph_step(st, tgt, stacked_src_imgs, n_scales, need_grad, fresh)
@@ -219,14 +226,15 @@ class SFMLearnerLoss:
             if tgt is rp.tensors[0] and len(bound) == len(rp.tensors) - 2 and all(a is b for a, b in zip(rp.tensors[2:], bound)) \
                     and stacked_src_imgs.data_ptr() == rp.ptrs[1]:
                 rp.st, rp.tgt, rp.stacked = st, tgt, stacked_src_imgs
-                rp.n_scales, rp.n_sources, rp.norm_batch = n_scales, n_sources, norm_batch
+                rp.n_scales, rp.n_sources, rp.norm_batch, rp.k_grad = n_scales, n_sources, norm_batch, k_grad
                 self._repeat = rp
-        return self._finish(st, inputs, n_scales, n_sources, do_exp, need_grad, run, frames)
+        return self._finish(st, inputs, n_scales, n_sources, do_exp, need_grad, run, frames, k_grad)
 
-    def _finish(self, st, inputs, n_scales, n_sources, do_exp, need_grad, run, frames):
+    def _finish(self, st, inputs, n_scales, n_sources, do_exp, need_grad, run, frames, k_grad=False):
         """The Function node of this call and the five reported scalars (models/base_model.py:117-124)."""
         st.calls += 1
-        node = _FusedLossFunction(st.fused, n_scales, n_sources, do_exp, need_grad, run, st if self.cache_buffers else None, frames)
+        node = _FusedLossFunction(st.fused, n_scales, n_sources, do_exp, need_grad, run, st if self.cache_buffers else None, frames,
+                                  k_grad and need_grad)
         total_loss = node(*inputs)
         for key, value in zip(_REPORTED, node.loss5.unbind(0)):
             report({key: value}, self)

@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from ._lib import SfmLossDesc, check, lib
 
-__all__ = ["pose_proj_fwd", "pose_proj_bwd", "warp_fwd", "warp_bwd", "sampler_fwd", "sampler_bwd",
+__all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss"]
 
 FLOAT32 = (torch.float32,)
@@ -94,6 +94,17 @@ def pose_proj_bwd(pose6, K, g_proj):
     return out
 
 
+def pose_proj_bwd_intrinsics(pose6, K, g_proj):
+    """The K half of `pose_proj_bwd` (sfm_pose_proj_bwd_k): g_proj (N,4,4) -> d_K (N,3,3) = g_proj[:, :3, :] . [R|t]^T."""
+    pose6, K, g_proj = _dev(pose6, "pose6", 2), _dev(K, "K", 3), _dev(g_proj, "g_proj", 3)
+    N = pose6.shape[0]
+    if pose6.shape[1] != 6 or tuple(K.shape) != (N, 3, 3) or tuple(g_proj.shape) != (N, 4, 4):
+        raise TypeError("pose6 must be (N,6), K (N,3,3) and g_proj (N,4,4)")
+    out = torch.empty((N, 3, 3), dtype=torch.float32, device=pose6.device)
+    _launch(pose6.device, lib.sfm_pose_proj_bwd_k, _p(pose6), _p(K), _p(g_proj), _p(out), N)
+    return out
+
+
 def _warp_args(imgs, depth, pose6, K):
     imgs = _dev(imgs, "imgs", 4)
     N, Cc, H, W = imgs.shape
@@ -132,6 +143,21 @@ def warp_bwd(imgs, depth, pose6, K, g_warped, want_d_src=False):
     _launch(imgs.device, lib.sfm_warp_bwd, _p(imgs), _p(depth), drows, _p(pose6), _p(K), _p(g_warped), _p(d_depth), _p(d_pose),
             _p(d_src), _p(ws), nbytes, N, Cc, H, W)
     return d_depth, d_pose, d_src
+
+
+def warp_bwd_intrinsics(imgs, depth, pose6, K, g_warped):
+    """The output `warp_bwd` does not have (sfm_warp_intrinsics_bwd): d_K (N,3,3), the gradient of projective_inverse_warp with
+    respect to K for the upstream gradient g_warped.  No atomics: the same bits on every call."""
+    imgs, depth, drows, pose6, K, N, Cc, H, W = _warp_args(imgs, depth, pose6, K)
+    g_warped = _dev(g_warped, "g_warped", 4)
+    if g_warped.shape != imgs.shape:
+        raise TypeError("g_warped must have the shape of imgs")
+    d_K = torch.empty((N, 3, 3), dtype=torch.float32, device=imgs.device)
+    nbytes = lib.sfm_warp_intrinsics_bwd_workspace_bytes(N, H, W)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=imgs.device)
+    _launch(imgs.device, lib.sfm_warp_intrinsics_bwd, _p(imgs), _p(depth), drows, _p(pose6), _p(K), _p(g_warped), _p(d_K), _p(ws),
+            nbytes, N, Cc, H, W)
+    return d_K
 
 
 def _sampler_args(x, grid):
@@ -425,11 +451,15 @@ class FusedLoss:
         self._keep = None
 
     def bind(self, tgt_pyr, src_pyr, intrinsics, disps, poses, masks=None, norm_B=None, want_d_src=False, layout="planar",
-             want_warped=False, buffers=None):
+             want_warped=False, buffers=None, want_d_intrinsics=False, want_d_proj=False):
         """layout: "planar" -- tgt (B,3,h,w), src (B,3*n_src,h,w) as in the reference; "hwc" -- tgt (B,1,h,w,3),
         src (B,n_src,h,w,3) as written by `pyramid_hwc` (the faster layout for these kernels; same results).
         want_warped: `forward` / `forward_backward` also write `self.warped[s]` (B,n_src,3,h,w), the warped source images the
         loss was computed on (curr_proj_img, models/base_model.py:90-94; planar in both layouts).
+        want_d_intrinsics / want_d_proj: every gradient call (`backward`, `forward_backward`, `step_from_frames(grad=True)`) is
+        followed by ONE small launch (sfm_loss_proj_bwd) that leaves `self.d_intrinsics` (B,S,3,3), the gradient with respect to
+        the intrinsics, and / or `self.d_proj` (B,S,n_src,3,4), dL/dPm of every proj_tgt_to_src call -- both scaled by the gy of
+        that call.  Off (the default): not one launch or allocation more.
         buffers: optional dict of caller-owned arrays to use instead of allocating -- any of "d_disps", "d_poses", "d_masks",
         "warped" (lists, one array per scale / source), "d_srcs" (one array or None per scale: replaces `want_d_src`; the caller's
         arrays are cleared before every backward like the own ones), "loss5" ((5,) float32) and "ws" (a contiguous device tensor of
@@ -461,8 +491,17 @@ class FusedLoss:
         self._desc_ref, self._ws_arg, self._loss5_arg = C.byref(d), C.c_void_p(self._ws_ptr), _p(self.loss5)
         self.d_disps, self.d_poses, self.d_masks, self.warped = d_disps, d_poses, d_masks, warped
         self._d_src_all, self.d_srcs = d_src_all, (d_srcs if any(t is not None for t in d_srcs) else None)
+        S = len(hw)
+        self.d_intrinsics = torch.empty((B, S, 3, 3), dtype=torch.float32, device=dev) if want_d_intrinsics else None
+        self.d_proj = torch.empty((B, S, n_src, 3, 4), dtype=torch.float32, device=dev) if want_d_proj else None
+        self._proj_args = (_p(self.d_proj), _p(self.d_intrinsics)) if want_d_intrinsics or want_d_proj else None
         self._keep = keep
         return self
+
+    def _proj_bwd(self, loss):
+        """sfm_loss_proj_bwd behind a gradient call (loss: 0 after sfm_loss_bwd, 1 after sfm_loss_fwd_bwd / sfm_step_fwd_bwd)"""
+        if self._proj_args is not None:
+            _launch(self.device, lib.sfm_loss_proj_bwd, self._desc_ref, loss, self._ws_arg, self._ws_bytes, *self._proj_args)
 
     def _check_inputs(self, tgt_pyr, src_pyr, intrinsics, disps, poses, masks, layout):
         """bind's arguments as contiguous float32 device arrays of consistent shapes, in the order of `_keep`"""
@@ -549,6 +588,8 @@ class FusedLoss:
         loss5, l5 = self._loss5(out)
         _launch(self.device, lib.sfm_step_fwd_bwd if grad else lib.sfm_step_fwd, tgt_full.data_ptr(), src_full.data_ptr(),
                 self._desc_ref, l5, self._ws_arg, self._ws_bytes)
+        if grad:
+            self._proj_bwd(1)
         return loss5
 
     def forward(self, out=None):
@@ -560,6 +601,7 @@ class FusedLoss:
     def backward(self, gy=1.0):
         self._zero_d_src()
         _launch(self.device, lib.sfm_loss_bwd, self._desc_ref, float(gy), self._ws_arg, self._ws_bytes)
+        self._proj_bwd(0)
         return self.d_disps, self.d_poses, self.d_masks, self.d_srcs
 
     def forward_backward(self, out=None, variant=0):
@@ -571,4 +613,5 @@ class FusedLoss:
         if variant:
             check(lib.sfm_loss_variant(int(variant)))
         _launch(self.device, lib.sfm_loss_fwd_bwd, self._desc_ref, l5, self._ws_arg, self._ws_bytes)
+        self._proj_bwd(1)
         return loss5

@@ -4,15 +4,17 @@ The reference's networks (DispNet, PoseNet) are Chainer links; on this stack the
 grad_fn.  This module hands those outputs to libsfmwarp and the gradients it computes back to torch.autograd:
 
   sfm_learner_loss / SFMLearnerLoss   the loss of models/base_model.py:48-124 as a function and as a torch.nn.Module
-  projective_inverse_warp             models/transform.py:156-193 (ops.warp_fwd / ops.warp_bwd)
+  projective_inverse_warp             models/transform.py:156-193 (ops.warp_fwd / ops.warp_bwd / ops.warp_bwd_intrinsics)
+  multi_scale_intrinsics              datasets/kitti/kitti_raw_transformed.py:76-93, differentiable (plain torch)
   disp_activation                     models/disp_net.py:104-122 (ops.disp_act_fwd / ops.disp_act_bwd)
   resize_images / resize_like         F.resize_images as DispNet's decoder differentiates it, models/disp_net.py:11-14,105,111,117
                                       (ops.resize / ops.resize_bwd)
 
-The loss is two custom operators (torch.library), so that FakeTensor and torch.compile can trace it:
+The loss is custom operators (torch.library), so that FakeTensor and torch.compile can trace it:
 
   sfmwarp::sfm_learner_loss   ONE fused call computes the five scalars and, when a gradient is wanted, every gradient for gy = 1
                               (sfm_step_fwd_bwd; the planar pyramid + sfm_loss_fwd_bwd for frames of HWC_MAX_PIXELS or more)
+  sfmwarp::sfm_learner_loss_k the same call followed by sfm_loss_proj_bwd: also the gradient of the intrinsics (used when they require one)
   sfmwarp::scale_arrays       its backward: those gradients times the upstream gradient, which the kernel reads on the device
                               (sfm_scale_arrays), written out of place
 
@@ -33,7 +35,7 @@ from . import _lib, ops
 from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
-           "scale_arrays_into"]
+           "scale_arrays_into", "multi_scale_intrinsics"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -43,11 +45,12 @@ def _round(n):
     return (n + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
-def _grad_spans(disps, poses, masks):
-    """[offset0, numel0, offset1, numel1, ...] of the unit-gradient arrays d_disp[s], d_pose[i], d_mask[s] (in that order) inside
-    the one buffer the loss op returns, that buffer's length in floats, and the arrays' shapes."""
+def _grad_spans(disps, poses, masks, K=None):
+    """[offset0, numel0, offset1, numel1, ...] of the unit-gradient arrays d_disp[s], d_pose[i], d_mask[s] (in that order) and, with
+    `K` (the intrinsics, when their gradient is wanted), d_intrinsics behind them inside the one buffer the loss op returns, that
+    buffer's length in floats, and the arrays' shapes."""
     spans, off, shapes = [], 0, []
-    for t in list(disps) + list(poses) + list(masks):
+    for t in list(disps) + list(poses) + list(masks) + ([K] if K is not None else []):
         n = t.numel()
         spans += [off, n]
         off += _round(n)
@@ -147,10 +150,11 @@ _FAKE = 0x1000             # placeholder pointer for sizing the workspace: never
 _desc_hook = None           # measurement hook (tools/torch_step_time.py): called with the descriptor bytes of every launch
 
 
-def _plan(B, H, W, n_src, disps, masks, poses, cfg):
+def _plan(B, H, W, n_src, disps, masks, poses, cfg, K=None):
+    """K: the intrinsics when the call also returns their gradient (a span of its own behind the others), else None"""
     S = len(disps)
     shapes = tuple(tuple(t.shape) for t in disps)
-    key = (B, H, W, n_src, shapes, len(masks), cfg)
+    key = (B, H, W, n_src, shapes, len(masks), cfg, K is not None)
     p = _PLANS.get(key)
     if p is not None:
         return p
@@ -180,18 +184,20 @@ def _plan(B, H, W, n_src, disps, masks, poses, cfg):
             p.src_off.append(None)
     p.ws_off = off
     p.scratch = off + _round(p.ws_bytes // 4) + _ALIGN    # + the slack to put the workspace on a 256-byte boundary
-    p.spans, p.grad_floats, _ = _grad_spans(disps, poses, masks)
+    p.spans, p.grad_floats, _ = _grad_spans(disps, poses, masks, K)
     if len(_PLANS) >= _MAX_PLANS:
         _PLANS.pop(next(iter(_PLANS)))            # the oldest configuration (e.g. an epoch's last, smaller batch)
     _PLANS[key] = p
     return p
 
 
-def _run_loss(tgt, src, K, disps, poses, masks, cfg, grad):
+def _run_loss(tgt, src, K, disps, poses, masks, cfg, grad, grad_k=False):
+    """grad_k (with grad): one more launch, sfm_loss_proj_bwd, leaves d_intrinsics for gy = 1 in the last span of the buffer"""
     dev = tgt.device
     B, _, H, W = tgt.shape
     n_src = len(poses)
-    p = _plan(B, H, W, n_src, disps, masks, poses, cfg)
+    grad_k = grad and grad_k
+    p = _plan(B, H, W, n_src, disps, masks, poses, cfg, K if grad_k else None)
     d = SfmLossDesc.from_buffer_copy(p.desc)
     scratch = torch.empty((p.scratch,), dtype=torch.float32, device=dev)
     base = scratch.data_ptr()
@@ -236,53 +242,64 @@ def _run_loss(tgt, src, K, disps, poses, masks, cfg, grad):
             if S > 1:
                 ops._launch(dev, lib.sfm_pyramid_fwd, x.data_ptr(), (C.c_void_p * S)(*pyr[:S]), B, G, H, W, S)
         ops._launch(dev, lib.sfm_loss_fwd_bwd if grad else lib.sfm_loss_fwd, C.byref(d), l5, ws, p.ws_bytes)
+    if grad_k and B > 0:
+        ops._launch(dev, lib.sfm_loss_proj_bwd, C.byref(d), 1, ws, p.ws_bytes, None, C.c_void_p(gb + 4 * p.spans[-2]))
     return loss5, g
 
 
-@torch.library.custom_op("sfmwarp::sfm_learner_loss", mutates_args=())
-def _loss_op(tgt_img: Tensor, src_imgs: Tensor, intrinsics: Tensor, disps: list[Tensor], poses: list[Tensor],
+def _loss_op_body(grad_k):
+    def body(tgt_img: Tensor, src_imgs: Tensor, intrinsics: Tensor, disps: list[Tensor], poses: list[Tensor],
              masks: list[Tensor], smooth_reg: float, exp_reg: float, ssim_rate: float, smooth_mode: int, projection: int,
              norm_batch: int, grad: bool) -> list[Tensor]:
-    """The fused loss on validated arrays: tgt_img (B,3,H,W), src_imgs (B,3*n_src,H,W), intrinsics (B,S,3,3), disps[s] (B,1,h,w),
-    poses[i] (B,6), masks[s] (B,n_src,h,w) or no masks (an empty list: no explainability term) -- float32, contiguous, one device.
-    smooth_mode / projection: _lib.SMOOTH_* / _lib.SFM_PROJECTION_*.
+        cfg = (float(smooth_reg), float(exp_reg), float(ssim_rate), int(smooth_mode), int(projection), int(norm_batch))
+        loss5, unit = _run_loss(tgt_img, src_imgs, intrinsics, disps, poses, masks, cfg, grad, grad_k)
+        return [loss5[0], loss5[1:].clone(), unit]          # (an operator's outputs may not share storage)
+    return body
+
+
+def _register_loss_op(name, grad_k):
+    """sfmwarp::<name>: the fused loss on validated arrays: tgt_img (B,3,H,W), src_imgs (B,3*n_src,H,W), intrinsics (B,S,3,3),
+    disps[s] (B,1,h,w), poses[i] (B,6), masks[s] (B,n_src,h,w) or no masks (an empty list: no explainability term) -- float32,
+    contiguous, one device.  smooth_mode / projection: _lib.SMOOTH_* / _lib.SFM_PROJECTION_*.
 
     Returns [total (), terms (4,) = (pixel, smooth, exp, ssim), unit_grads]: unit_grads is ONE flat float32 buffer that holds
     d_disp[s], d_pose[i], d_mask[s] -- the gradients of total for gy = 1, in that order, each at an offset rounded up to 64
-    floats (_grad_spans) -- when `grad`, else empty."""
-    cfg = (float(smooth_reg), float(exp_reg), float(ssim_rate), int(smooth_mode), int(projection), int(norm_batch))
-    loss5, unit = _run_loss(tgt_img, src_imgs, intrinsics, disps, poses, masks, cfg, grad)
-    return [loss5[0], loss5[1:].clone(), unit]          # (an operator's outputs may not share storage)
+    floats (_grad_spans) -- when `grad`, else empty.  grad_k (the operator sfm_learner_loss_k, same arguments): d_intrinsics
+    (B,S,3,3) follows them, and the backward hands it to `intrinsics`.  (Two operators, not one with a flag: the first keeps its
+    signature, and a traced call drops a trailing argument that equals its default.)"""
+    op = torch.library.custom_op("sfmwarp::" + name, mutates_args=())(_loss_op_body(grad_k))
+
+    @op.register_fake
+    def _(tgt_img, src_imgs, intrinsics, disps, poses, masks, smooth_reg, exp_reg, ssim_rate, smooth_mode, projection, norm_batch,
+          grad):
+        n = _grad_spans(disps, poses, masks, intrinsics if grad and grad_k else None)[1]
+        f = dict(dtype=torch.float32, device=tgt_img.device)
+        return [torch.empty((), **f), torch.empty((4,), **f), torch.empty((n if grad else 0,), **f)]
+
+    def setup_context(ctx, inputs, output):
+        disps, poses, masks = inputs[3], inputs[4], inputs[5]
+        ctx.grad = inputs[12]
+        ctx.spans, _, ctx.shapes = _grad_spans(disps, poses, masks, inputs[2] if ctx.grad and grad_k else None)
+        ctx.counts = (len(disps), len(poses), len(masks))
+        ctx.mark_non_differentiable(output[1], output[2])
+        ctx.save_for_backward(output[2])
+
+    def backward(ctx, grads):
+        S, n, m = ctx.counts
+        (unit,) = ctx.saved_tensors
+        if not ctx.grad:        # no prediction required a gradient (only an image or the intrinsics did): none flows anywhere
+            return (None, None, None, [None] * S, [None] * n, [None] * m, None, None, None, None, None, None, None)
+        gy = grads[0].to(torch.float32)
+        views = _views(torch.ops.sfmwarp.scale_arrays(unit, ctx.spans, gy), ctx.spans, ctx.shapes)
+        return (None, None, views[S + n + m] if grad_k else None, views[:S], views[S:S + n], views[S + n:S + n + m],
+                None, None, None, None, None, None, None)
+
+    op.register_autograd(backward, setup_context=setup_context)
+    return op
 
 
-@_loss_op.register_fake
-def _(tgt_img, src_imgs, intrinsics, disps, poses, masks, smooth_reg, exp_reg, ssim_rate, smooth_mode, projection, norm_batch,
-      grad):
-    n = _grad_spans(disps, poses, masks)[1]
-    f = dict(dtype=torch.float32, device=tgt_img.device)
-    return [torch.empty((), **f), torch.empty((4,), **f), torch.empty((n if grad else 0,), **f)]
-
-
-def _setup_context(ctx, inputs, output):
-    disps, poses, masks = inputs[3], inputs[4], inputs[5]
-    ctx.spans, _, ctx.shapes = _grad_spans(disps, poses, masks)
-    ctx.counts = (len(disps), len(poses), len(masks))
-    ctx.grad = inputs[12]
-    ctx.mark_non_differentiable(output[1], output[2])
-    ctx.save_for_backward(output[2])
-
-
-def _backward(ctx, grads):
-    S, n, m = ctx.counts
-    (unit,) = ctx.saved_tensors
-    if not ctx.grad:        # no prediction required a gradient (only an image or the intrinsics did): none flows anywhere
-        return (None, None, None, [None] * S, [None] * n, [None] * m, None, None, None, None, None, None, None)
-    gy = grads[0].to(torch.float32)
-    views = _views(torch.ops.sfmwarp.scale_arrays(unit, ctx.spans, gy), ctx.spans, ctx.shapes)
-    return (None, None, None, views[:S], views[S:S + n], views[S + n:], None, None, None, None, None, None, None)
-
-
-_loss_op.register_autograd(_backward, setup_context=_setup_context)
+_loss_op = _register_loss_op("sfm_learner_loss", False)
+_loss_k_op = _register_loss_op("sfm_learner_loss_k", True)
 
 
 class _LossFunction(torch.autograd.Function):
@@ -291,23 +308,26 @@ class _LossFunction(torch.autograd.Function):
     torch.compile traces the custom operator instead (sfm_learner_loss)."""
 
     @staticmethod
-    def forward(ctx, tgt, src, K, cfg, grad, S, n, *arrays):
+    def forward(ctx, tgt, src, K, cfg, grad, grad_k, S, n, *arrays):
         disps, poses, masks = list(arrays[:S]), list(arrays[S:S + n]), list(arrays[S + n:])
-        loss5, unit = _run_loss(tgt, src, K, disps, poses, masks, cfg, grad)
+        loss5, unit = _run_loss(tgt, src, K, disps, poses, masks, cfg, grad, grad_k)
         terms = loss5[1:]
         ctx.mark_non_differentiable(terms)
         ctx.set_materialize_grads(False)              # (no zero-filled gradient for `terms`: one fill kernel less per step)
         ctx.save_for_backward(unit)                   # (freed by a backward without retain_graph, like any saved tensor)
-        ctx.grad = grad
-        ctx.spans, _, ctx.shapes = _grad_spans(disps, poses, masks)
+        ctx.grad, ctx.grad_k = grad, grad and grad_k
+        ctx.spans, _, ctx.shapes = _grad_spans(disps, poses, masks, K if ctx.grad_k else None)
         return loss5[0], terms
 
     @staticmethod
     def backward(ctx, g_total, g_terms):
         (unit,) = ctx.saved_tensors
         if g_total is None or not ctx.grad:     # (not ctx.grad: only an image or the intrinsics required a gradient)
-            return (None,) * (7 + len(ctx.shapes))
-        return (None,) * 7 + tuple(_views(_scaled(unit, ctx.spans, _gy(g_total.to(torch.float32))), ctx.spans, ctx.shapes))
+            return (None,) * (8 + len(ctx.shapes) - ctx.grad_k)
+        views = _views(_scaled(unit, ctx.spans, _gy(g_total.to(torch.float32))), ctx.spans, ctx.shapes)
+        if ctx.grad_k:          # (the last span: d_intrinsics, scaled in the same launch as the others)
+            return (None, None, views[-1]) + (None,) * 5 + tuple(views[:-1])
+        return (None,) * 8 + tuple(views)
 
 
 def _dev_float(t, name, ndim=None):
@@ -341,8 +361,12 @@ def sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred
                      ssim_rate=0., smooth_mode="second_order", projection="fast", norm_batch=None):
     """The loss of SFMLearner.__call__ (models/base_model.py:48-124) with torch.autograd gradients.
 
-    tgt_img (B,3,H,W) and src_imgs (B,n_src,3,H,W): float32 images; intrinsics (B,S,3,3) float32 -- constants, as the reference's
-      `.data` makes them (:71-72): no gradient flows to them.
+    tgt_img (B,3,H,W) and src_imgs (B,n_src,3,H,W): float32 images -- constants, as the reference's `.data` makes them (:71-72): no
+      gradient flows to them.
+    intrinsics (B,S,3,3) float32: any invertible 3x3 per (sample, scale).  When it requires grad (a learned calibration, e.g. a
+      (B,4) focal / centre parameter through `multi_scale_intrinsics`) it receives its gradient WITH the predictions': one more small
+      launch (sfm_loss_proj_bwd) behind the fused one, scaled by the upstream gradient in the same launch as the others.  With every
+      prediction detached no gradient launch runs and the intrinsics get none either.
     pred_disps: S tensors (B,1,H>>s,W>>s); pred_poses: n_src tensors (B,6) (views such as h.split(6, 1) are fine) or one packed
       (B,6*n_src) tensor; pred_maskes: S explainability logits (B,n_src,H>>s,W>>s), needed iff exp_reg > 0.  Float32, bfloat16 or
       float16 (autocast) on a ROCm device: computed in float32, each gradient returned in its input's dtype.
@@ -390,13 +414,15 @@ def sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred
         if t.device != tgt.device:
             raise TypeError("every array must live on %s, one is on %s" % (tgt.device, t.device))
     grad = torch.is_grad_enabled() and any(t.requires_grad for t in disps + poses + masks)
+    grad_k = grad and K.requires_grad
     cfg = (float(smooth_reg or 0.0), exp_reg, float(ssim_rate or 0.0), smooth_mode, projection,
            int(norm_batch if norm_batch is not None else B))
     stacked = src.view(B, 3 * n_src, H, W)
     if torch.compiler.is_compiling():
-        total, terms, _ = torch.ops.sfmwarp.sfm_learner_loss(tgt, stacked, K, disps, poses, masks, *cfg, grad)
+        op = torch.ops.sfmwarp.sfm_learner_loss_k if grad_k else torch.ops.sfmwarp.sfm_learner_loss
+        total, terms, _ = op(tgt, stacked, K, disps, poses, masks, *cfg, grad)
         return total, terms
-    return _LossFunction.apply(tgt, stacked, K, cfg, grad, S, n_src, *disps, *poses, *masks)
+    return _LossFunction.apply(tgt, stacked, K, cfg, grad, grad_k, S, n_src, *disps, *poses, *masks)
 
 
 class SFMLearnerLoss(torch.nn.Module):
@@ -447,14 +473,38 @@ class _Warp(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         imgs, depthes, poses, K = ctx.saved_tensors
-        d_depth, d_pose, d_src = ops.warp_bwd(imgs, depthes, poses, K, g.contiguous(), want_d_src=ctx.needs_input_grad[0])
-        return d_src, d_depth.view(depthes.shape), d_pose, None
+        g = g.contiguous()
+        d_depth, d_pose, d_src = ops.warp_bwd(imgs, depthes, poses, K, g, want_d_src=ctx.needs_input_grad[0])
+        d_K = ops.warp_bwd_intrinsics(imgs, depthes, poses, K, g) if ctx.needs_input_grad[3] else None
+        return d_src, d_depth.view(depthes.shape), d_pose, d_K
 
 
 def projective_inverse_warp(imgs, depthes, poses, K):
     """models/transform.py:156-193: imgs (N,C,H,W), depthes (N,3,H*W) or (N,H*W), poses (N,6), K (N,3,3), float32 on a ROCm
-    device -> the warped images (N,C,H,W).  Gradients flow to imgs, depthes and poses (ops.warp_bwd), not to K."""
+    device -> the warped images (N,C,H,W).  Gradients flow to imgs, depthes and poses (ops.warp_bwd) and, when it requires one, to K
+    (ops.warp_bwd_intrinsics: one more pass over the pixels)."""
     return _Warp.apply(imgs, depthes, poses, K)
+
+
+def multi_scale_intrinsics(K, n_scales):
+    """get_multi_scale_intrinsics, datasets/kitti/kitti_raw_transformed.py:76-93, for a batch and differentiable (plain torch, any
+    device): K (B,3,3) -- fx, fy, cx, cy are read from [0,0], [1,1], [0,2], [1,2], as the reference does -- or (B,4) = (fx, fy, cx,
+    cy), e.g. a learned parameter -> (B,n_scales,3,3): scale s is [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] with the four divided by
+    2**s.  What `sfm_learner_loss` takes as `intrinsics`."""
+    if not isinstance(K, torch.Tensor) or not K.is_floating_point():
+        raise TypeError("multi_scale_intrinsics: expected a floating-point torch.Tensor")
+    if K.dim() == 3 and tuple(K.shape[1:]) == (3, 3):
+        f = torch.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], dim=1)
+    elif K.dim() == 2 and K.shape[1] == 4:
+        f = K
+    else:
+        raise TypeError("multi_scale_intrinsics: K must be (B,3,3) or (B,4) = (fx, fy, cx, cy), got %s" % (tuple(K.shape),))
+    if not 1 <= int(n_scales) <= _lib.SFM_MAX_SCALES:
+        raise TypeError("n_scales must be in [1, %d]" % _lib.SFM_MAX_SCALES)
+    v = torch.stack([f / float(2 ** s) for s in range(int(n_scales))], dim=1)     # (B,S,4); no host array goes to the device
+    zero, one = torch.zeros_like(v[..., 0]), torch.ones_like(v[..., 0])
+    rows = [v[..., 0], zero, v[..., 2], zero, v[..., 1], v[..., 3], zero, zero, one]
+    return torch.stack(rows, dim=-1).reshape(f.shape[0], int(n_scales), 3, 3)
 
 
 class _DispAct(torch.autograd.Function):
