@@ -1,4 +1,4 @@
-"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h, include/sfmwarp_intrinsics.h).  No torch types cross this boundary:
+"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h, include/sfmwarp_intrinsics.h, include/sfmwarp_warp_pyramid.h).  No torch types cross this boundary:
 every tensor is handed over as a raw device pointer plus explicit sizes.
 
 The library is REQUIRED: there is no CPU or PyTorch fallback.  If it is missing, importing
@@ -65,6 +65,18 @@ class SfmLossDesc(C.Structure):
     ]
 
 
+class SfmWarpPyramidDesc(C.Structure):
+    """include/sfmwarp_warp_pyramid.h"""
+    _fields_ = [
+        ("B", C.c_int32), ("n_src", C.c_int32), ("n_scales", C.c_int32),
+        ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
+        ("image_layout", C.c_int32),
+        ("src", _FP * SFM_MAX_SCALES), ("disp", _FP * SFM_MAX_SCALES), ("intrinsics", _FP), ("pose", _FP * SFM_MAX_SRC),
+        ("warped", _FP * SFM_MAX_SCALES), ("valid", _FP * SFM_MAX_SCALES),
+        ("g_warped", _FP * SFM_MAX_SCALES), ("d_disp", _FP * SFM_MAX_SCALES), ("d_pose", _FP * SFM_MAX_SRC),
+    ]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -118,6 +130,14 @@ INTRINSICS_SYMBOLS = {
 }
 
 
+# every symbol declared in include/sfmwarp_warp_pyramid.h (the differentiable warp of the whole source pyramid)
+WARP_PYRAMID_SYMBOLS = {
+    "sfm_warp_pyramid_fwd": (_I, [C.POINTER(SfmWarpPyramidDesc), _V]),
+    "sfm_warp_pyramid_bwd_workspace_bytes": (_Z, [C.POINTER(SfmWarpPyramidDesc)]),
+    "sfm_warp_pyramid_bwd": (_I, [C.POINTER(SfmWarpPyramidDesc), _V, _Z, _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -128,7 +148,8 @@ def _load():
             "libsfmwarp.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(INTRINSICS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(INTRINSICS_SYMBOLS.items()) \
+            + list(WARP_PYRAMID_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

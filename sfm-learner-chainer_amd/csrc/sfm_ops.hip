@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "sfm_common.h"
+#include "sfm_warp_pixel.h"
 #include "sfmwarp_ext.h"
 #include "sfmwarp_intrinsics.h"
 
@@ -62,17 +63,6 @@ __global__ void pose_proj_fwd_kernel(const float* __restrict__ pose6, const floa
   o[15] = 1.f;
 }
 
-// gT3 (3x4) = K^T . gPm[0:3, :]   (K4^T . gPm restricted to the rows that reach R and t)
-__device__ __forceinline__ void kt_times_gpm(const float* K, const float* gPm3x4, float* gT3, bool accumulate) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float v = K[0 * 3 + i] * gPm3x4[0 * 4 + j] + K[1 * 3 + i] * gPm3x4[1 * 4 + j] + K[2 * 3 + i] * gPm3x4[2 * 4 + j];
-      gT3[i * 4 + j] = accumulate ? gT3[i * 4 + j] + v : v;
-    }
-}
-
 __global__ void pose_proj_bwd_kernel(const float* __restrict__ pose6, const float* __restrict__ K,
                                      const float* __restrict__ g_proj, float* __restrict__ d_pose6, int N) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,91 +76,11 @@ __global__ void pose_proj_bwd_kernel(const float* __restrict__ pose6, const floa
 }
 
 // ------------------------------------------------------------------------------------------
-// F.spatial_transformer_sampler (call site models/transform.py:189): general semantics on the
-// zero-padded image, for arbitrary grids
-// ------------------------------------------------------------------------------------------
-struct PadTap {
-  int u0, v0;             // top-left tap in PADDED coordinates, u0 in [0,W], v0 in [0,H]
-  float wx0, wx1, wy0, wy1;
-  bool ok_u, ok_v;        // coordinate inside the padded image (gradient mask)
-};
-
-__device__ __forceinline__ PadTap pad_taps(float gx, float gy, int H, int W) {
-#pragma clang fp contract(off)
-  PadTap t;
-  const float up = (gx + 1.0f) * (float)(W - 1) * 0.5f + 1.0f;
-  const float vp = (gy + 1.0f) * (float)(H - 1) * 0.5f + 1.0f;
-  const float uc = fminf(fmaxf(up, 0.0f), (float)(W + 1));
-  const float vc = fminf(fmaxf(vp, 0.0f), (float)(H + 1));
-  t.u0 = min(max((int)floorf(uc), 0), W);
-  t.v0 = min(max((int)floorf(vc), 0), H);
-  t.wx0 = (float)(t.u0 + 1) - uc;
-  t.wx1 = uc - (float)t.u0;
-  t.wy0 = (float)(t.v0 + 1) - vc;
-  t.wy1 = vc - (float)t.v0;
-  t.ok_u = (up >= 0.0f) && (up <= (float)(W + 1));
-  t.ok_v = (vp >= 0.0f) && (vp <= (float)(H + 1));
-  return t;
-}
-
-__device__ __forceinline__ float pad_read(const float* img, int v, int u, int H, int W) {  // padded coords
-  return (u >= 1 && u <= W && v >= 1 && v <= H) ? img[(v - 1) * W + (u - 1)] : 0.0f;
-}
-
-// ------------------------------------------------------------------------------------------
-// projective_inverse_warp  (models/transform.py:156-193) -- the API-parity operator.
-//
-// Unlike the fused loss kernels (which pre-multiply the geometry), this operator keeps the REFERENCE'S
-// evaluation order, step by step and without fused multiply-adds:
-//   ray = K^-1 . (x, y, 1)                         transform.py:105-106   (batch_matmul: left to right over k)
-//   c   = D (.) ray ; c4 = (c, 1)                  :107-108
-//   q   = Pm . c4 ; z = q2 + 1e-10                 :122-123
-//   xn  = (q0 / z) / ((W-1)/2.) - 1 ; yn likewise  :124-125
-//   each component not strictly inside (-1, 1) is doubled   :128-131
-//   F.spatial_transformer_sampler on the zero-padded image  :189  (pad_taps / pad_read above)
-// so that the set of exactly-zero output pixels and the sampling positions are the reference's own.
+// projective_inverse_warp  (models/transform.py:156-193) -- the API-parity operator: the per-pixel chain in the reference's own
+// evaluation order is sfm_warp_pixel.h (PadTap / pad_taps / pad_read, RefProj / ref_project, load_depth3, WarpGq / warp_pixel_gq).
 // one block = 256 consecutive pixels of one sample; the block's geometry is built once in LDS
 // ------------------------------------------------------------------------------------------
 constexpr int WARP_BLOCK = 256;
-
-struct RefProj {
-  float ray[3], c[3];   // K^-1 . pix ; D (.) ray
-  float z, U, V;        // q2 + 1e-10 ; q0 / z ; q1 / z
-  float mx, my;         // 1 inside (-1, 1), else 2     (transform.py:128-130)
-  float gx, gy;         // the grid coordinates handed to the sampler (xn * mx, yn * my)
-};
-
-__device__ __forceinline__ RefProj ref_project(const Geom& g, const float xf, const float yf, const float* D, const int H, const int W) {
-#pragma clang fp contract(off)
-  RefProj r;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    r.ray[j] = (g.Kinv[j * 3 + 0] * xf + g.Kinv[j * 3 + 1] * yf) + g.Kinv[j * 3 + 2];   // the third coordinate of pix is 1
-    r.c[j] = D[j] * r.ray[j];
-  }
-  float q[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) q[k] = ((g.P[k * 4 + 0] * r.c[0] + g.P[k * 4 + 1] * r.c[1]) + g.P[k * 4 + 2] * r.c[2]) + g.P[k * 4 + 3];
-  r.z = q[2] + 1e-10f;
-  r.U = q[0] / r.z;
-  r.V = q[1] / r.z;
-  const float half_w = (float)((double)(W - 1) / 2.0), half_h = (float)((double)(H - 1) / 2.0);
-  const float xn = r.U / half_w - 1.0f, yn = r.V / half_h - 1.0f;
-  r.mx = (xn > -1.0f && xn < 1.0f) ? 1.0f : 2.0f;     // NaN compares false: doubled, stays NaN
-  r.my = (yn > -1.0f && yn < 1.0f) ? 1.0f : 2.0f;
-  r.gx = xn * r.mx;
-  r.gy = yn * r.my;
-  return r;
-}
-
-__device__ __forceinline__ void load_depth3(const float* depth, const int n, const int drows, const int P, const int j, float* D) {
-  if (drows == 1) {   // one row of the reference's (N,3,H*W) broadcast (base_model.py:82-84)
-    D[0] = D[1] = D[2] = depth[(size_t)n * P + j];
-  } else {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) D[r] = depth[((size_t)n * 3 + r) * P + j];
-  }
-}
 
 __global__ void __launch_bounds__(WARP_BLOCK) warp_fwd_kernel(const float* __restrict__ src, const float* __restrict__ depth,
                                                               const float* __restrict__ pose6, const float* __restrict__ K,
@@ -188,63 +98,12 @@ __global__ void __launch_bounds__(WARP_BLOCK) warp_fwd_kernel(const float* __res
   load_depth3(depth, n, drows, P, j, D);
   const RefProj r = ref_project(g, (float)x, (float)y, D, H, W);
   const PadTap t = pad_taps(r.gx, r.gy, H, W);
-  const float w1 = t.wx0 * t.wy0, w2 = t.wx1 * t.wy0, w3 = t.wx0 * t.wy1, w4 = t.wx1 * t.wy1;
+  const auto taps = PlanarImage{src + (size_t)n * C * P, (size_t)P}.fetch(t, H, W);
   for (int c = 0; c < C; ++c) {
-    const float* img = src + ((size_t)n * C + c) * P;
-    float v = w1 * pad_read(img, t.v0, t.u0, H, W);
-    v += w2 * pad_read(img, t.v0, t.u0 + 1, H, W);
-    v += w3 * pad_read(img, t.v0 + 1, t.u0, H, W);
-    v += w4 * pad_read(img, t.v0 + 1, t.u0 + 1, H, W);
-    warped[((size_t)n * C + c) * P + j] = v;
+    float x4[4];
+    taps.get(c, x4);
+    warped[((size_t)n * C + c) * P + j] = pad_blend(t, x4);
   }
-}
-
-// per pixel: the reference's backward chain sampler -> x mask -> normalisation -> perspective division, i.e. dL/dq of q = Pm . c4
-// (transform.py:122-131,189 backward), and the sampler's scatter into d_src when that is bound.  ONE function for sfm_warp_bwd and
-// sfm_warp_intrinsics_bwd: the two differentiate the same dL/dq.
-struct WarpGq {
-  RefProj r;
-  float gq[3];
-};
-
-__device__ __forceinline__ WarpGq warp_pixel_gq(const Geom& g, const float* __restrict__ src, const float* __restrict__ depth,
-                                                const float* __restrict__ g_warped, float* __restrict__ d_src, const int n, const int C,
-                                                const int H, const int W, const int drows, const int j) {
-#pragma clang fp contract(off)
-  WarpGq o;
-  const int P = H * W;
-  const int y = j / W, x = j - y * W;
-  float D[3];
-  load_depth3(depth, n, drows, P, j, D);
-  o.r = ref_project(g, (float)x, (float)y, D, H, W);
-  const RefProj& r = o.r;
-  const PadTap t = pad_taps(r.gx, r.gy, H, W);
-  float gu = 0.f, gv = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float* img = src + ((size_t)n * C + c) * P;
-    const float gc = g_warped[((size_t)n * C + c) * P + j];
-    const float x1 = pad_read(img, t.v0, t.u0, H, W), x2 = pad_read(img, t.v0, t.u0 + 1, H, W);
-    const float x3 = pad_read(img, t.v0 + 1, t.u0, H, W), x4 = pad_read(img, t.v0 + 1, t.u0 + 1, H, W);
-    gu += gc * (-t.wy0 * x1 + t.wy0 * x2 - t.wy1 * x3 + t.wy1 * x4);
-    gv += gc * (-t.wx0 * x1 - t.wx1 * x2 + t.wx0 * x3 + t.wx1 * x4);
-    if (d_src) {
-      float* dst = d_src + ((size_t)n * C + c) * P;
-      const int u = t.u0, v = t.v0;   // padded coordinates: taps on the zero frame receive nothing
-      if (u >= 1 && u <= W && v >= 1 && v <= H) atomicAdd(dst + (v - 1) * W + (u - 1), gc * t.wx0 * t.wy0);
-      if (u + 1 >= 1 && u + 1 <= W && v >= 1 && v <= H) atomicAdd(dst + (v - 1) * W + u, gc * t.wx1 * t.wy0);
-      if (u >= 1 && u <= W && v + 1 >= 1 && v + 1 <= H) atomicAdd(dst + v * W + (u - 1), gc * t.wx0 * t.wy1);
-      if (u + 1 >= 1 && u + 1 <= W && v + 1 >= 1 && v + 1 <= H) atomicAdd(dst + v * W + u, gc * t.wx1 * t.wy1);
-    }
-  }
-  // sampler backward to the grid, then p_s_xy *= mask (transform.py:131)
-  const float ggx = t.ok_u ? gu * ((float)(W - 1) * 0.5f) : 0.f;
-  const float ggy = t.ok_v ? gv * ((float)(H - 1) * 0.5f) : 0.f;
-  const float half_w = (float)((double)(W - 1) / 2.0), half_h = (float)((double)(H - 1) / 2.0);
-  const float gU = (ggx * r.mx) / half_w, gV = (ggy * r.my) / half_h;
-  o.gq[0] = gU / r.z;
-  o.gq[1] = gV / r.z;
-  o.gq[2] = -(gU * r.U + gV * r.V) / r.z;
-  return o;
 }
 
 // per pixel: dL/dq (warp_pixel_gq), d_depth, and the 12 sums of gPm (block-reduced into ws)
@@ -265,23 +124,19 @@ __global__ void __launch_bounds__(WARP_BLOCK) warp_bwd_kernel(const float* __res
 #pragma unroll
   for (int k = 0; k < 12; ++k) acc[k] = 0.f;
   if (j < P) {
-    const WarpGq w = warp_pixel_gq(g, src, depth, g_warped, d_src, n, C, H, W, drows, j);
-    const RefProj& r = w.r;
-    const float gq0 = w.gq[0], gq1 = w.gq[1], gq2 = w.gq[2];
-    // g_c = Pm^T . gq ; g_depthes[j] = g_c[j] * ray[j]   (transform.py:107,122 backward)
-    const float gd0 = ((g.P[0] * gq0 + g.P[4] * gq1) + g.P[8] * gq2) * r.ray[0];
-    const float gd1 = ((g.P[1] * gq0 + g.P[5] * gq1) + g.P[9] * gq2) * r.ray[1];
-    const float gd2 = ((g.P[2] * gq0 + g.P[6] * gq1) + g.P[10] * gq2) * r.ray[2];
+    float D[3], gd[3];
+    load_depth3(depth, n, drows, P, j, D);
+    const size_t img0 = (size_t)n * C * P;
+    const WarpGq w = warp_pixel_gq(g, PlanarImage{src + img0, (size_t)P}, D, g_warped + img0, d_src ? d_src + img0 : nullptr, C, H, W, j);
+    warp_pixel_gdepth(g, w, gd);
     if (drows == 1) {
-      d_depth[(size_t)n * P + j] = (gd0 + gd1) + gd2;     // broadcast_to backward: sum of the three rows
+      d_depth[(size_t)n * P + j] = (gd[0] + gd[1]) + gd[2];     // broadcast_to backward: sum of the three rows
     } else {
-      d_depth[((size_t)n * 3 + 0) * P + j] = gd0;
-      d_depth[((size_t)n * 3 + 1) * P + j] = gd1;
-      d_depth[((size_t)n * 3 + 2) * P + j] = gd2;
+      d_depth[((size_t)n * 3 + 0) * P + j] = gd[0];
+      d_depth[((size_t)n * 3 + 1) * P + j] = gd[1];
+      d_depth[((size_t)n * 3 + 2) * P + j] = gd[2];
     }
-    acc[0] = gq0 * r.c[0]; acc[1] = gq0 * r.c[1]; acc[2] = gq0 * r.c[2];  acc[3] = gq0;
-    acc[4] = gq1 * r.c[0]; acc[5] = gq1 * r.c[1]; acc[6] = gq1 * r.c[2];  acc[7] = gq1;
-    acc[8] = gq2 * r.c[0]; acc[9] = gq2 * r.c[1]; acc[10] = gq2 * r.c[2]; acc[11] = gq2;
+    warp_pixel_gpm(w, acc);
   }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
@@ -324,15 +179,15 @@ __global__ void __launch_bounds__(WARP_BLOCK) warp_intr_bwd_kernel(const float* 
 #pragma unroll
   for (int k = 0; k < INTR_SUMS; ++k) acc[k] = 0.f;
   if (j < P) {
-    const WarpGq w = warp_pixel_gq(g, src, depth, g_warped, nullptr, n, C, H, W, drows, j);
-    const RefProj& r = w.r;
-    const int y = j / W, x = j - y * W;
-    const float xf = (float)x, yf = (float)y;
     float D[3];
     load_depth3(depth, n, drows, P, j, D);
+    const size_t img0 = (size_t)n * C * P;
+    const WarpGq w = warp_pixel_gq(g, PlanarImage{src + img0, (size_t)P}, D, g_warped + img0, nullptr, C, H, W, j);
+    const int y = j / W, x = j - y * W;
+    const float xf = (float)x, yf = (float)y;
+    warp_pixel_gpm(w, acc);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      acc[k * 4 + 0] = w.gq[k] * r.c[0]; acc[k * 4 + 1] = w.gq[k] * r.c[1]; acc[k * 4 + 2] = w.gq[k] * r.c[2]; acc[k * 4 + 3] = w.gq[k];
       const float g_ray = D[k] * ((g.P[0 * 4 + k] * w.gq[0] + g.P[1 * 4 + k] * w.gq[1]) + g.P[2 * 4 + k] * w.gq[2]);
       acc[12 + k * 3 + 0] = g_ray * xf; acc[12 + k * 3 + 1] = g_ray * yf; acc[12 + k * 3 + 2] = g_ray;
     }
@@ -671,16 +526,6 @@ __device__ __forceinline__ float resize_blend(const ResizeTap& t, const float a0
 
 __device__ __forceinline__ float resize_read(const ResizeTap& t, const float* img, const int W) {
   return resize_blend(t, img[t.v0 * W + t.u0], img[t.v0 * W + t.u1], img[t.v1 * W + t.u0], img[t.v1 * W + t.u1]);
-}
-
-// the scale a flat index over several scales belongs to: the last s >= FIRST with j >= begin[s]
-template <int FIRST, typename Index>
-__device__ __forceinline__ int scale_of(const Index j, const Index* begin, const int n_scales) {
-  int s = FIRST;
-#pragma unroll
-  for (int k = FIRST + 1; k < SFM_MAX_SCALES; ++k)
-    if (k < n_scales && j >= begin[k]) s = k;
-  return s;
 }
 
 __global__ void resize_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int oH, int oW) {

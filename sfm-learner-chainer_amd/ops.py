@@ -9,10 +9,11 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SfmLossDesc, check, lib
+from ._lib import SfmLossDesc, SfmWarpPyramidDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
-           "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss"]
+           "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
+           "warp_pyramid_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -432,6 +433,82 @@ def _place_workspace(ws, nbytes, device):
     if ws.data_ptr() % 256:
         ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=device)
     return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, nbytes
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the warp of the whole source pyramid (include/sfmwarp_warp_pyramid.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _warp_pyramid_desc(src_pyr, disps, poses, K, layout):
+    """(descriptor with the inputs bound, the arrays it points at, B, n_src, [(h, w)], device) for warp_pyramid_fwd / _bwd"""
+    if layout not in _LAYOUTS:
+        raise ValueError("layout must be 'planar' or 'hwc', got %r" % (layout,))
+    hwc = layout == "hwc"
+    S, n_src = len(disps), len(poses)
+    if len(src_pyr) != S or not 1 <= S <= _lib.SFM_MAX_SCALES or not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("src_pyr and disps need one entry per scale (1..%d), poses one per source (1..%d)"
+                        % (_lib.SFM_MAX_SCALES, _lib.SFM_MAX_SRC))
+    src_pyr, disps, poses = _devs(src_pyr, "src_pyr", 5 if hwc else 4), _devs(disps, "disps", 4), _devs(poses, "poses", 2)
+    K = _dev(K, "intrinsics", 4)
+    B, dev = disps[0].shape[0], disps[0].device
+    if tuple(K.shape) != (B, S, 3, 3):
+        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
+    hw = [tuple(t.shape[2:]) for t in disps]
+    for s, (h, w) in enumerate(hw):
+        want = (B, n_src, h, w, 3) if hwc else (B, 3 * n_src, h, w)
+        if tuple(src_pyr[s].shape) != want or tuple(disps[s].shape) != (B, 1, h, w):
+            raise TypeError("scale %d: expected src %s and disp (B,1,h,w), got %s and %s"
+                            % (s, want, tuple(src_pyr[s].shape), tuple(disps[s].shape)))
+    for i, t in enumerate(poses):
+        if tuple(t.shape) != (B, 6):
+            raise TypeError("poses[%d] must be (B,6)" % i)
+    for t in src_pyr + disps + poses + [K]:
+        if t.device != dev:
+            raise TypeError("every array must live on %s, one is on %s" % (dev, t.device))
+    d = SfmWarpPyramidDesc()
+    d.B, d.n_src, d.n_scales, d.image_layout = B, n_src, S, _LAYOUTS[layout]
+    for s, (h, w) in enumerate(hw):
+        d.H[s], d.W[s] = h, w
+    d.intrinsics = K.data_ptr()
+    for field, arrays in ((d.src, src_pyr), (d.disp, disps), (d.pose, poses)):
+        _point(field, arrays)
+    return d, (src_pyr, disps, poses, K), B, n_src, hw, dev
+
+
+def warp_pyramid_fwd(src_pyr, disps, poses, K, layout, want_valid=False):
+    """Every scale and source of a step warped in ONE launch (sfm_warp_pyramid_fwd): src_pyr[s] (B,3*n_src,h,w) for layout
+    "planar" or (B,n_src,h,w,3) for "hwc" (what `pyramid_hwc` writes), disps[s] (B,1,h,w), poses[i] (B,6), K (B,S,3,3) ->
+    [warped_s (B,n_src,3,h,w)], each `warp_fwd` of that (scale, source) with depth 1 / disp bit for bit; with `want_valid` also
+    [valid_s (B,n_src,h,w)]: 1.0 where the sample passes both strict tests of models/transform.py:129, else 0.0."""
+    d, keep, B, n_src, hw, dev = _warp_pyramid_desc(src_pyr, disps, poses, K, layout)
+    warped = _empty([(B, n_src, 3, h, w) for h, w in hw], dev)
+    valid = _empty([(B, n_src, h, w) for h, w in hw], dev) if want_valid else None
+    _point(d.warped, warped)
+    _point(d.valid, valid or ())
+    _launch(dev, lib.sfm_warp_pyramid_fwd, C.byref(d))
+    return (warped, valid) if want_valid else warped
+
+
+def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped):
+    """The backward of `warp_pyramid_fwd` for the upstream gradients g_warped[s] (B,n_src,3,h,w): one launch over the pixels and a
+    small fold (sfm_warp_pyramid_bwd) -> ([d_disp_s (B,1,h,w)], [d_pose_i (B,6)]).  No atomics: the same bits on every call."""
+    d, keep, B, n_src, hw, dev = _warp_pyramid_desc(src_pyr, disps, poses, K, layout)
+    if len(g_warped) != len(hw):
+        raise TypeError("g_warped needs one entry per scale")
+    g_warped = _devs(g_warped, "g_warped", 5)
+    for s, (h, w) in enumerate(hw):
+        if tuple(g_warped[s].shape) != (B, n_src, 3, h, w) or g_warped[s].device != dev:
+            raise TypeError("g_warped[%d] must be (B,n_src,3,h,w) = %s on %s" % (s, (B, n_src, 3, h, w), dev))
+    d_disps = _empty([(B, 1, h, w) for h, w in hw], dev)
+    d_poses = _empty([(B, 6)] * n_src, dev)
+    for field, arrays in ((d.g_warped, g_warped), (d.d_disp, d_disps), (d.d_pose, d_poses)):
+        _point(field, arrays)
+    nbytes = lib.sfm_warp_pyramid_bwd_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        check(lib.sfm_warp_pyramid_bwd(C.byref(d), None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid warp pyramid descriptor")
+    ws, ptr, have = _place_workspace(None, nbytes, dev)
+    _launch(dev, lib.sfm_warp_pyramid_bwd, C.byref(d), C.c_void_p(ptr), have)
+    return d_disps, d_poses
 
 
 class FusedLoss:

@@ -5,6 +5,8 @@ grad_fn.  This module hands those outputs to libsfmwarp and the gradients it com
 
   sfm_learner_loss / SFMLearnerLoss   the loss of models/base_model.py:48-124 as a function and as a torch.nn.Module
   projective_inverse_warp             models/transform.py:156-193 (ops.warp_fwd / ops.warp_bwd / ops.warp_bwd_intrinsics)
+  warp_pyramid                        the warped source images of EVERY (scale, source) of a step, models/base_model.py:69-94, for a
+                                      loss of the caller's own (ops.pyramid_hwc, ops.warp_pyramid_fwd / ops.warp_pyramid_bwd)
   multi_scale_intrinsics              datasets/kitti/kitti_raw_transformed.py:76-93, differentiable (plain torch)
   disp_activation                     models/disp_net.py:104-122 (ops.disp_act_fwd / ops.disp_act_bwd)
   resize_images / resize_like         F.resize_images as DispNet's decoder differentiates it, models/disp_net.py:11-14,105,111,117
@@ -35,7 +37,7 @@ from . import _lib, ops
 from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
-           "scale_arrays_into", "multi_scale_intrinsics"]
+           "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -484,6 +486,77 @@ def projective_inverse_warp(imgs, depthes, poses, K):
     device -> the warped images (N,C,H,W).  Gradients flow to imgs, depthes and poses (ops.warp_bwd) and, when it requires one, to K
     (ops.warp_bwd_intrinsics: one more pass over the pixels)."""
     return _Warp.apply(imgs, depthes, poses, K)
+
+
+class _WarpPyramid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, K, S, want_valid, *arrays):
+        disps, poses = list(arrays[:S]), list(arrays[S:])
+        pyr = ops.pyramid_hwc(src, S)
+        out = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", want_valid)
+        warped, valid = out if want_valid else (out, [])
+        ctx.save_for_backward(K, *pyr, *disps, *poses)
+        ctx.S = S
+        ctx.mark_non_differentiable(*valid)
+        ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
+        return tuple(warped) + tuple(valid)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        S = ctx.S
+        K, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        pyr, disps, poses = list(saved[:S]), list(saved[S:2 * S]), list(saved[2 * S:])
+        B, n_src = pyr[0].shape[:2]
+        g = [torch.zeros((B, n_src, 3) + tuple(d.shape[2:]), dtype=torch.float32, device=d.device) if gr is None
+             else gr.to(torch.float32).contiguous() for gr, d in zip(grads[:S], disps)]
+        d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", g)
+        return (None, None, None, None) + tuple(d_disps) + tuple(d_poses)
+
+
+def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False):
+    """The warped source images of every scale and every source of a step -- curr_proj_img of models/base_model.py:90-94 for all s
+    and i -- as differentiable tensors, for a loss of your own on them (a per-pixel minimum over the sources, auto-masking, a
+    robust penalty, a feature loss).  The inputs are those of `sfm_learner_loss`:
+
+    src_imgs (B,n_src,3,H,W) float32: constants, as in the loss -- no gradient flows to them;
+    intrinsics (B,S,3,3) float32, any invertible 3x3 per (sample, scale): a constant HERE -- if it requires grad this raises
+      TypeError: `projective_inverse_warp`, per (scale, source), is the route that differentiates K;
+    pred_disps: S tensors (B,1,H>>s,W>>s); pred_poses: n_src tensors (B,6) or one packed (B,6*n_src) tensor; float32, bfloat16 or
+      float16 on a ROCm device, computed in float32, each gradient returned in its input's dtype.
+
+    Returns a list of S tensors (B,n_src,3,H>>s,W>>s): [s][:, i] is projective_inverse_warp of source i at scale s with depth
+    1 / disp (bit for bit), exactly 0 where the sample is not in view.  With `return_valid` also the list of S masks (B,n_src,H>>s,W>>s),
+    1.0 where the sample passes both strict tests of models/transform.py:129, else 0.0 (not differentiable).
+
+    Two launches forward (the source pyramid, the warp of all scales and sources); backward one launch over the pixels plus a small
+    fold, whatever S and n_src are.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture."""
+    src = ops._dev(src_imgs, "src_imgs", 5)
+    B, n_src, c, H, W = src.shape
+    if c != 3:
+        raise TypeError("src_imgs must be (B,n_src,3,H,W), got %s" % (tuple(src.shape),))
+    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d source images, got %d" % (_lib.SFM_MAX_SRC, n_src))
+    S = len(pred_disps)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
+    K = ops._dev(intrinsics, "intrinsics", 4)
+    if tuple(K.shape) != (B, S, 3, 3):
+        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
+    if K.requires_grad:
+        raise TypeError("warp_pyramid does not differentiate the intrinsics: detach them, or warp per (scale, source) with "
+                        "projective_inverse_warp, which returns their gradient")
+    disps = []
+    for s, t in enumerate(pred_disps):
+        t = _dev_float(t, "pred_disps[%d]" % s, 4)
+        if tuple(t.shape) != (B, 1, H >> s, W >> s):
+            raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s, got %s" % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
+        disps.append(t)
+    poses = _poses(pred_poses, B, n_src)
+    for t in [K] + disps + poses:
+        if t.device != src.device:
+            raise TypeError("every array must live on %s, one is on %s" % (src.device, t.device))
+    out = _WarpPyramid.apply(src.view(B, 3 * n_src, H, W), K, S, bool(return_valid), *disps, *poses)
+    return (list(out[:S]), list(out[S:])) if return_valid else list(out)
 
 
 def multi_scale_intrinsics(K, n_scales):
