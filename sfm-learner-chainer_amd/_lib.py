@@ -1,4 +1,5 @@
-"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h, include/sfmwarp_intrinsics.h, include/sfmwarp_warp_pyramid.h).  No torch types cross this boundary:
+"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h, include/sfmwarp_intrinsics.h, include/sfmwarp_warp_pyramid.h,
+include/sfmwarp_photo_error.h).  No torch types cross this boundary:
 every tensor is handed over as a raw device pointer plus explicit sizes.
 
 The library is REQUIRED: there is no CPU or PyTorch fallback.  If it is missing, importing
@@ -77,6 +78,17 @@ class SfmWarpPyramidDesc(C.Structure):
     ]
 
 
+class SfmPhotoErrorDesc(C.Structure):
+    """include/sfmwarp_photo_error.h"""
+    _fields_ = [
+        ("B", C.c_int32), ("n_img", C.c_int32), ("n_scales", C.c_int32),
+        ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
+        ("ssim_rate", C.c_float),
+        ("img", _FP * SFM_MAX_SCALES), ("tgt", _FP * SFM_MAX_SCALES), ("err", _FP * SFM_MAX_SCALES),
+        ("g_err", _FP * SFM_MAX_SCALES), ("d_img", _FP * SFM_MAX_SCALES),
+    ]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -138,6 +150,13 @@ WARP_PYRAMID_SYMBOLS = {
 }
 
 
+# every symbol declared in include/sfmwarp_photo_error.h (the per-pixel L1 + SSIM error maps of a warped pyramid)
+PHOTO_ERROR_SYMBOLS = {
+    "sfm_photo_error_fwd": (_I, [C.POINTER(SfmPhotoErrorDesc), _V]),
+    "sfm_photo_error_bwd": (_I, [C.POINTER(SfmPhotoErrorDesc), _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -149,7 +168,7 @@ def _load():
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(INTRINSICS_SYMBOLS.items()) \
-            + list(WARP_PYRAMID_SYMBOLS.items()):
+            + list(WARP_PYRAMID_SYMBOLS.items()) + list(PHOTO_ERROR_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -9,11 +9,11 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SfmLossDesc, SfmWarpPyramidDesc, check, lib
+from ._lib import SfmLossDesc, SfmPhotoErrorDesc, SfmWarpPyramidDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
-           "warp_pyramid_bwd"]
+           "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -509,6 +509,67 @@ def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped):
     ws, ptr, have = _place_workspace(None, nbytes, dev)
     _launch(dev, lib.sfm_warp_pyramid_bwd, C.byref(d), C.c_void_p(ptr), have)
     return d_disps, d_poses
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the per-pixel photometric error maps of a warped pyramid (include/sfmwarp_photo_error.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _photo_error_desc(imgs, tgts, ssim_rate):
+    """(descriptor with the inputs bound, the arrays it points at, B, n_img, [(h, w)], device) for photo_error_fwd / _bwd"""
+    if not isinstance(imgs, (list, tuple)) or not isinstance(tgts, (list, tuple)):
+        raise TypeError("imgs and tgts must be lists with one array per scale")
+    S = len(imgs)
+    if len(tgts) != S or not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("imgs and tgts need one entry per scale (1..%d), got %d and %d" % (_lib.SFM_MAX_SCALES, S, len(tgts)))
+    imgs, tgts = _devs(imgs, "imgs", 5), _devs(tgts, "tgts", 4)
+    B, n_img = imgs[0].shape[:2]
+    dev = imgs[0].device
+    if not 1 <= n_img <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d images per sample, got %d" % (_lib.SFM_MAX_SRC, n_img))
+    hw = [tuple(t.shape[3:]) for t in imgs]
+    for s, (h, w) in enumerate(hw):
+        if tuple(imgs[s].shape) != (B, n_img, 3, h, w) or tuple(tgts[s].shape) != (B, 3, h, w):
+            raise TypeError("scale %d: expected imgs (B,n_img,3,h,w) = %s and tgts (B,3,h,w), got %s and %s"
+                            % (s, (B, n_img, 3, h, w), tuple(imgs[s].shape), tuple(tgts[s].shape)))
+    for t in imgs + tgts:
+        if t.device != dev:
+            raise TypeError("every array must live on %s, one is on %s" % (dev, t.device))
+    d = SfmPhotoErrorDesc()
+    d.B, d.n_img, d.n_scales, d.ssim_rate = B, n_img, S, float(ssim_rate)
+    for s, (h, w) in enumerate(hw):
+        d.H[s], d.W[s] = h, w
+    for field, arrays in ((d.img, imgs), (d.tgt, tgts)):
+        _point(field, arrays)
+    return d, (imgs, tgts), B, n_img, hw, dev
+
+
+def photo_error_fwd(imgs, tgts, ssim_rate):
+    """The photometric error map of every (scale, image) of a step in ONE launch (sfm_photo_error_fwd): imgs[s] (B,n_img,3,h,w) --
+    what `warp_pyramid_fwd` returns, or the planar source pyramid viewed so --, tgts[s] (B,3,h,w) -> [err_s (B,n_img,h,w)],
+    err = (1 - ssim_rate) * mean_c |X - Y| + ssim_rate * mean_c compute_ssim(X, Y) of models/base_model.py:126-142 per pixel.  A
+    rejection by the library (ssim_rate outside [0,1]) is a ValueError with sfm_last_error() as its message."""
+    d, keep, B, n_img, hw, dev = _photo_error_desc(imgs, tgts, ssim_rate)
+    err = _empty([(B, n_img, h, w) for h, w in hw], dev)
+    _point(d.err, err)
+    _launch(dev, lib.sfm_photo_error_fwd, C.byref(d))
+    return err
+
+
+def photo_error_bwd(imgs, tgts, ssim_rate, g_err):
+    """The backward of `photo_error_fwd` for the upstream gradients g_err[s] (B,n_img,h,w), ONE launch (sfm_photo_error_bwd) ->
+    [d_img_s (B,n_img,3,h,w)].  The targets are constants.  No atomics: the same bits on every call."""
+    d, keep, B, n_img, hw, dev = _photo_error_desc(imgs, tgts, ssim_rate)
+    if not isinstance(g_err, (list, tuple)) or len(g_err) != len(hw):
+        raise TypeError("g_err needs one entry per scale")
+    g_err = _devs(g_err, "g_err", 4)
+    for s, (h, w) in enumerate(hw):
+        if tuple(g_err[s].shape) != (B, n_img, h, w) or g_err[s].device != dev:
+            raise TypeError("g_err[%d] must be (B,n_img,h,w) = %s on %s" % (s, (B, n_img, h, w), dev))
+    d_imgs = _empty([(B, n_img, 3, h, w) for h, w in hw], dev)
+    for field, arrays in ((d.g_err, g_err), (d.d_img, d_imgs)):
+        _point(field, arrays)
+    _launch(dev, lib.sfm_photo_error_bwd, C.byref(d))
+    return d_imgs
 
 
 class FusedLoss:

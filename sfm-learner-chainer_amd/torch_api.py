@@ -7,6 +7,8 @@ grad_fn.  This module hands those outputs to libsfmwarp and the gradients it com
   projective_inverse_warp             models/transform.py:156-193 (ops.warp_fwd / ops.warp_bwd / ops.warp_bwd_intrinsics)
   warp_pyramid                        the warped source images of EVERY (scale, source) of a step, models/base_model.py:69-94, for a
                                       loss of the caller's own (ops.pyramid_hwc, ops.warp_pyramid_fwd / ops.warp_pyramid_bwd)
+  photometric_error                   alpha * SSIM + (1 - alpha) * L1 per pixel (models/base_model.py:96,126-142) of every (scale, image) of
+                                      a step, differentiable w.r.t. the images (ops.photo_error_fwd / ops.photo_error_bwd)
   multi_scale_intrinsics              datasets/kitti/kitti_raw_transformed.py:76-93, differentiable (plain torch)
   disp_activation                     models/disp_net.py:104-122 (ops.disp_act_fwd / ops.disp_act_bwd)
   resize_images / resize_like         F.resize_images as DispNet's decoder differentiates it, models/disp_net.py:11-14,105,111,117
@@ -37,7 +39,7 @@ from . import _lib, ops
 from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
-           "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid"]
+           "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -557,6 +559,81 @@ def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=F
             raise TypeError("every array must live on %s, one is on %s" % (src.device, t.device))
     out = _WarpPyramid.apply(src.view(B, 3 * n_src, H, W), K, S, bool(return_valid), *disps, *poses)
     return (list(out[:S]), list(out[S:])) if return_valid else list(out)
+
+
+class _PhotoError(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ssim_rate, S, *arrays):
+        imgs, tgts = list(arrays[:S]), list(arrays[S:])
+        err = ops.photo_error_fwd(imgs, tgts, ssim_rate)
+        ctx.save_for_backward(*imgs, *tgts)
+        ctx.S, ctx.ssim_rate = S, ssim_rate
+        ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
+        return tuple(err)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        S = ctx.S
+        imgs, tgts = list(ctx.saved_tensors[:S]), list(ctx.saved_tensors[S:])
+        g = [torch.zeros(x.shape[:2] + x.shape[3:], dtype=torch.float32, device=x.device) if gr is None
+             else gr.to(torch.float32).contiguous() for gr, x in zip(grads, imgs)]
+        d_imgs = ops.photo_error_bwd(imgs, tgts, ctx.ssim_rate, g)
+        return (None, None) + tuple(d_imgs) + (None,) * S
+
+
+def photometric_error(imgs, tgt, *, ssim_rate):
+    """The per-pixel photometric error of every (scale, image) of a step -- ssim_rate * compute_ssim + (1 - ssim_rate) * |.| of
+    models/base_model.py:96,126-142 before any mean, averaged over the three channels -- as differentiable maps: the stage between
+    `warp_pyramid` and a minimum over the sources, an auto-mask or a robust penalty of your own.
+
+    imgs: a list of S tensors (B,n,3,h_s,w_s), float32, bfloat16 or float16 on a ROCm device (computed in float32, the gradient
+      returned in the input's dtype): what `warp_pyramid` returns, or any such list -- the planar source pyramid viewed as
+      (B,n,3,h,w) gives the identity-reprojection error that auto-masking compares with;
+    tgt: the target frames (B,3,H,W) float32 -- turned into the planar pyramid of `sfm_learner_loss` (ops.pyramid), and then
+      h_s, w_s must be H >> s, W >> s -- or a list of S per-scale tensors (B,3,h_s,w_s).  A constant: no gradient flows to it;
+    ssim_rate: alpha in [0,1]; 0 is the mean absolute difference alone (no SSIM code runs), 1 the SSIM term alone.
+
+    Returns a list of S maps (B,n,h_s,w_s) in [0,1] for images in [-1,1].  The SSIM window is the reference's zero-padded 3x3
+    average (not Monodepth2's reflection padding), and nothing is masked: the zeros of out-of-view pixels take part in their
+    neighbours' windows as in the reference -- `warp_pyramid(..., return_valid=True)` has the mask.
+
+    One launch forward and one backward, whatever S and n are (plus the pyramid launch for a single `tgt`).  The gradient goes to
+    `imgs` only; if none of them requires one, nothing is recorded.  Nothing reads a device value on the host: it runs under
+    torch.cuda.graph capture."""
+    if not isinstance(imgs, (list, tuple)):
+        raise TypeError("imgs must be a list of (B,n,3,h,w) tensors, one per scale")
+    S = len(imgs)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
+    xs = []
+    for s, t in enumerate(imgs):
+        t = _dev_float(t, "imgs[%d]" % s, 5)
+        if t.shape[2] != 3 or tuple(t.shape[:2]) != tuple(xs[0].shape[:2] if xs else t.shape[:2]):
+            raise TypeError("imgs[%d] must be (B,n,3,h,w) with the B and n of imgs[0], got %s" % (s, tuple(t.shape)))
+        xs.append(t)
+    B, n = xs[0].shape[:2]
+    if not 1 <= n <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d images per sample, got %d" % (_lib.SFM_MAX_SRC, n))
+    if isinstance(tgt, (list, tuple)):
+        if len(tgt) != S:
+            raise TypeError("imgs has %d scales but tgt has %d" % (S, len(tgt)))
+        tgts = ops._devs(tgt, "tgt", 4)
+    else:
+        tgt = ops._dev(tgt, "tgt", 4)
+        H, W = tgt.shape[2:]
+        for s, t in enumerate(xs):
+            if tuple(t.shape[3:]) != (H >> s, W >> s):
+                raise TypeError("imgs[%d] must be (B,n,3,H>>%d,W>>%d) = %s for a tgt of %s, got %s"
+                                % (s, s, s, (B, n, 3, H >> s, W >> s), tuple(tgt.shape), tuple(t.shape)))
+        if tuple(tgt.shape[:2]) != (B, 3):
+            raise TypeError("tgt must be (B,3,H,W) = (%d,3,H,W), got %s" % (B, tuple(tgt.shape)))
+        tgts = ops.pyramid(tgt.detach(), S)
+    for s, (x, y) in enumerate(zip(xs, tgts)):
+        if tuple(y.shape) != (B, 3) + tuple(x.shape[3:]):
+            raise TypeError("tgt[%d] must be (B,3,h,w) = %s, got %s" % (s, (B, 3) + tuple(x.shape[3:]), tuple(y.shape)))
+        if x.device != xs[0].device or y.device != xs[0].device:
+            raise TypeError("every array must live on %s" % (xs[0].device,))
+    return list(_PhotoError.apply(float(ssim_rate), S, *xs, *[y.detach() for y in tgts]))
 
 
 def multi_scale_intrinsics(K, n_scales):
