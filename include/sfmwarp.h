@@ -299,6 +299,179 @@ int sfm_scale_arrays(const float *const *x, float *const *y, const long long *nu
 int sfm_augment_fwd(const float *imgs, const float *params, float *out, int B, int F, int C, int H, int W, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The backward of sfm_resize_fwd.
+ * ---------------------------------------------------------------------------------------- */
+#define SFM_RESIZE_MAX_TERMS 8
+/* Backward of F.resize_images (models/disp_net.py:14,105,111,117; the adjoint of the loop head models/base_model.py:70-72):
+ *   gx (N,C,H,W), OVERWRITTEN  =  sum over k < n_terms of  R_k^T gy[k],   gy[k] (N,C,oH[k],oW[k]),
+ * R_k = sfm_resize_fwd to (oH[k], oW[k]).  n_terms = 1: the plain backward.  n_terms = S with oH[k] = H >> k, oW[k] = W >> k:
+ * the adjoint of sfm_pyramid_fwd including scale 0 (d_src[] of the fused loss -> the gradient of the full-resolution frames).
+ * gy, oH, oW: HOST arrays of n_terms entries.  No atomics; the sum runs in a fixed order (k, then oy, then ox, ascending):
+ * two calls on the same inputs agree bit for bit.
+ * Any N*C (no grid limit), any H, W, oH[k], oW[k] >= 1; N = 0 is validated like any call, launches nothing, and its gx and gy[k] may
+ * be NULL.  Errors, checked in this order before any HIP call: gy, oH or oW NULL, or gx NULL while N != 0 -> SFM_ERR_NULL; n_terms
+ * outside 1..SFM_RESIZE_MAX_TERMS -> SFM_ERR_SHAPE; N < 0, C, H or W < 1 -> SFM_ERR_SHAPE; per term oH[k] or oW[k] < 1 ->
+ * SFM_ERR_SHAPE, then gy[k] NULL while N > 0 -> SFM_ERR_NULL; N*C*H*W or the elements of all gy[k] together >= 2^40 -> SFM_ERR_SHAPE. */
+int sfm_resize_bwd(const float *const *gy, const int *oH, const int *oW, int n_terms, float *gx,
+                   int N, int C, int H, int W, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The gradient with respect to the camera intrinsics.
+ *
+ * The intrinsics enter the view synthesis twice (citations into pfnet/sfm-learner-chainer): Pm = K4 . [R|t] in proj_tgt_to_src
+ * (models/transform.py:86-88) and ray = K^-1 . pix through F.batch_inv in pixel2cam (:105).  With gPm = dL/dPm (rows 0..2):
+ *   dL/dK = gPm[:, 0:3] . R^T + gPm[:, 3] . t^T  -  K^-T . gKinv . K^-T ,   gKinv = dL/d(K^-1) = sum over pixels of g_ray (x) pix .
+ * With ONE depth per pixel (models/base_model.py:82-84) gKinv = (K R)^T . gPm[:, 0:3] . K^T, so the second term is
+ * K^-T . R^T . K^T . gPm[:, 0:3]: the gradient follows from gPm alone.
+ * ---------------------------------------------------------------------------------------- */
+/* The fused loss: dL/dPm and dL/d(intrinsics) from the pose sums that the gradient call has left in its workspace.
+ * Call it AFTER sfm_loss_bwd (loss = 0), or after sfm_loss_fwd_bwd / sfm_step_fwd_bwd (loss = 1), with the same descriptor bytes,
+ * the same `ws` and `ws_bytes` on the same stream, before anything else uses `ws`.  It reads `ws`, never writes it, and may be
+ * called more than once.
+ *   d_proj       (B, n_scales, n_src, 3, 4), overwritten: dL/dPm, rows 0..2, of each proj_tgt_to_src call of the loop
+ *                (models/base_model.py:90-94, models/transform.py:86-88); row 3 of Pm has zero gradient.
+ *   d_intrinsics (B, n_scales, 3, 3), overwritten: dL/d(intrinsics[b, s]) summed over the sources: both routes above, transform.py:86-88
+ *                and, through F.batch_inv, :105.
+ * Either may be NULL, not both.  Both carry the gy of the gradient call (it is in the sums); with norm_B > B they are this shard's
+ * additive share.
+ * One launch.  The tiles of a (sample, scale, source) are folded in a fixed order in fp64, K^-1 and the products formed in fp64
+ * and rounded once: two calls agree bit for bit.  The tile layout is found with the plan look-up of the gradient call (the
+ * library's own choice of kernel): after a gradient call that consumed sfm_loss_variant(4) or (5) the result is UNSPECIFIED
+ * (hook 3 leaves the layout alone).  B == 0 (an empty shard, whose input pointers may be NULL as for sfm_loss_bwd): only the first
+ * and the third check below are made, nothing is launched.
+ * Errors, checked in this order before any HIP call: desc NULL -> SFM_ERR_NULL; the descriptor rejected as by sfm_loss_bwd (its code);
+ * d_proj and d_intrinsics both NULL -> SFM_ERR_NULL; ws NULL, ws_bytes below sfm_loss_workspace_bytes' layout for this call or ws off
+ * the 256-byte boundary -> SFM_ERR_WORKSPACE. */
+int sfm_loss_proj_bwd(const SfmLossDesc *desc, int loss, const void *ws, size_t ws_bytes, float *d_proj, float *d_intrinsics,
+                      void *stream);
+
+/* The missing output of sfm_warp_bwd: d_K (N,3,3), overwritten, the gradient of projective_inverse_warp (models/transform.py:156-193)
+ * with respect to K for the upstream gradient g_warped -- through proj_tgt_to_src (:86-88) and through pixel2cam's F.batch_inv
+ * (:105-107; with depth_rows = 3 the three rows of `depthes` may differ, :107).  Arguments, shapes and checks as for sfm_warp_bwd:
+ * N = 0 returns at once; a NULL tensor -> SFM_ERR_NULL; N, C, H, W as there, depth_rows 1 or 3 -> SFM_ERR_SHAPE; ws NULL or shorter
+ * than sfm_warp_intrinsics_bwd_workspace_bytes(N, H, W) (4-byte aligned scratch) -> SFM_ERR_WORKSPACE.
+ * The pixels are re-projected in the reference's own order and dL/dq formed exactly as by sfm_warp_bwd (the same device code);
+ * block sums in fp32, folded in a fixed order in fp64, the products in fp64, rounded once.  No atomics: two calls agree bit for bit. */
+size_t sfm_warp_intrinsics_bwd_workspace_bytes(int N, int H, int W);
+int sfm_warp_intrinsics_bwd(const float *src, const float *depth, int depth_rows, const float *pose6, const float *K,
+                            const float *g_warped, float *d_K, void *ws, size_t ws_bytes, int N, int C, int H, int W, void *stream);
+
+/* The K half of sfm_pose_proj_bwd (models/transform.py:86-88, Pm = K4 . [R|t]):
+ *   pose6 (N,6), K (N,3,3), g_proj (N,4,4)  ->  d_K (N,3,3), overwritten  =  g_proj[0:3, :] . [R|t]^T   (row 3 of g_proj is not read;
+ * K is not read either -- the product is linear in it -- and is taken for symmetry with sfm_pose_proj_bwd: it must not be NULL).
+ * N = 0 returns at once; a NULL pointer -> SFM_ERR_NULL; N < 0 -> SFM_ERR_SHAPE. */
+int sfm_pose_proj_bwd_k(const float *pose6, const float *K, const float *g_proj, float *d_K, int N, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The differentiable warp of the whole source pyramid of one step.
+ *
+ * What it is for: a loss of the caller's own on the warped images -- a per-pixel minimum over the sources, auto-masking, a robust
+ * penalty, a feature loss -- with the gradient back through the warp.  The fused loss (sfm_loss_*) hands the warped images out
+ * (SfmLossDesc.warped) but takes no upstream gradient for them; sfm_warp_fwd / sfm_warp_bwd take one, for ONE (scale, source) per
+ * call.  These calls warp every scale and every source of a step in ONE launch (models/base_model.py:81-94 for all s and i) and
+ * differentiate them in ONE launch plus a small fold, from the inputs sfm_loss_* takes.
+ *
+ * Per pixel it is sfm_warp_fwd / sfm_warp_bwd with depth_rows = 1 and depth = 1 / disp (models/base_model.py:60; the correctly
+ * rounded quotient): the same device code in the reference's own evaluation order (models/transform.py:94-133,189), hence
+ *   warped[s][:, i] == sfm_warp_fwd(src[s][:, 3i:3i+3], 1 / disp[s], pose[i], intrinsics[:, s])   bit for bit, in both image layouts.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct SfmWarpPyramidDesc {
+  int32_t B, n_src, n_scales;
+  int32_t H[SFM_MAX_SCALES], W[SFM_MAX_SCALES];
+  int32_t image_layout;                       /* SFM_LAYOUT_* of src[]                        */
+  const float *src[SFM_MAX_SCALES];           /* (B,3*n_src,h,w) planar | (B,n_src,h,w,3) hwc */
+  const float *disp[SFM_MAX_SCALES];          /* (B,1,h,w)                                    */
+  const float *intrinsics;                    /* (B,n_scales,3,3), any invertible 3x3         */
+  const float *pose[SFM_MAX_SRC];             /* (B,6)                                        */
+  float *warped[SFM_MAX_SCALES];              /* fwd: (B,n_src,3,h,w) overwritten             */
+  float *valid[SFM_MAX_SCALES];               /* fwd: (B,n_src,h,w) or NULL                   */
+  const float *g_warped[SFM_MAX_SCALES];      /* bwd: (B,n_src,3,h,w)                         */
+  float *d_disp[SFM_MAX_SCALES];              /* bwd: (B,1,h,w) overwritten                   */
+  float *d_pose[SFM_MAX_SRC];                 /* bwd: (B,6) overwritten                       */
+} SfmWarpPyramidDesc;
+
+/* Forward, one launch: warped[s][b, i] = projective_inverse_warp(source i of src[s][b], 1 / disp[s][b], pose[i][b],
+ * intrinsics[b, s]) for every scale s < n_scales, source i < n_src and sample b < B; planar in both image layouts (the layout of
+ * SfmLossDesc.warped), exactly 0 where the sample is not in view.
+ * valid[s], where bound (any subset of the scales), overwritten: 1.0f where both strict tests of models/transform.py:129 hold
+ * (-1 < xn < 1 and -1 < yn < 1), else 0.0f -- 0 implies that the three warped channels are exactly 0.
+ * Reads src, disp, intrinsics, pose; ignores g_warped, d_disp, d_pose. */
+int sfm_warp_pyramid_fwd(const SfmWarpPyramidDesc *d, void *stream);
+
+/* Backward for the upstream gradients g_warped[s], one launch over the pixels plus a fold of one wavefront per (sample, source):
+ *   d_disp[s] = -(sum over i, ascending, of source i's d_depth as sfm_warp_bwd forms it with depth_rows = 1) / (disp * disp),
+ *               written once per pixel;
+ *   d_pose[i] = the pose backward of  sum over s, ascending, of  K_s^T . gPm[s, i]  (models/transform.py:43-91 backward), gPm[s, i]
+ *               the sum of that scale's block partials in a fixed order in fp64, rounded to fp32.
+ * No atomics: two calls on the same inputs agree bit for bit.  No gradient for the source images or the intrinsics
+ * (sfm_warp_bwd's d_src and sfm_warp_intrinsics_bwd provide those per scale and source).
+ * Reads src, disp, intrinsics, pose, g_warped; ignores warped and valid.
+ * ws: sfm_warp_pyramid_bwd_workspace_bytes(d) bytes of scratch on a 256-byte boundary (0 on a descriptor the backward rejects; a
+ * multiple of 256; 48 bytes per 256-pixel block and source).  Content undefined before and after the call. */
+size_t sfm_warp_pyramid_bwd_workspace_bytes(const SfmWarpPyramidDesc *d);
+int sfm_warp_pyramid_bwd(const SfmWarpPyramidDesc *d, void *ws, size_t ws_bytes, void *stream);
+
+/* Errors of both calls, checked in this order before any HIP call:
+ *   d NULL -> SFM_ERR_NULL;
+ *   n_src outside 1..SFM_MAX_SRC, n_scales outside 1..SFM_MAX_SCALES, B < 0, any H[s] or W[s] < 3, 3 * H[s] * W[s] >= 2^31, or
+ *     2^31 or more 256-pixel blocks in all -> SFM_ERR_SHAPE;
+ *   image_layout not SFM_LAYOUT_PLANAR or SFM_LAYOUT_HWC -> SFM_ERR_CONFIG;
+ *   B == 0: nothing more is checked, nothing is launched, 0 is returned (an empty shard's pointers may be NULL);
+ *   a pointer the call reads or writes is NULL (valid[s] excepted) -> SFM_ERR_NULL;
+ *   sfm_warp_pyramid_bwd: ws NULL, ws_bytes below the query's answer, or ws off the 256-byte boundary -> SFM_ERR_WORKSPACE.
+ * The pixel-interleaved layout needs no frame-size limit of its own here (sfm_loss_* forms a tap's byte offset in fp32 and is limited
+ * to 2^24 / 12 pixels per image; these kernels form it in integers). */
+
+/* ------------------------------------------------------------------------------------------
+ * The per-pixel photometric error maps of a whole warped pyramid.
+ *
+ * What it is for: the companion of sfm_warp_pyramid_*.  A loss of the caller's own on the warped images -- a per-pixel minimum over
+ * the sources, auto-masking against the unwarped source, a robust penalty -- is "alpha * SSIM + (1 - alpha) * L1 per pixel, then a
+ * minimum or a mask, then a mean".  The fused loss (sfm_loss_*) reduces its SSIM to a scalar at once and takes no upstream
+ * gradient; these calls hand out the per-pixel map of every (scale, image) of a step in ONE launch and differentiate it with
+ * respect to the images in ONE more, so that what remains for the caller works on small single-channel maps.
+ *
+ * Per sample b, image i, scale s, pixel p and channel c = 0..2, with X = img, Y = tgt and Pool the zero-padded 3x3 sum divided by 9
+ * always (F.average_pooling_2d(., 3, 1, 1)):
+ *   S_c    = the SSIM index of models/base_model.py:126-142 (c1 = 0.01^2, c2 = 0.03^2),   e_c = clip((1 - S_c) / 2, 0, 1)
+ *   err(p) = (1 - alpha) * (1/3) * sum_c |X_c - Y_c|(p)  +  alpha * (1/3) * sum_c e_c(p)
+ * This is the reference's own zero-padded window (not the reflection padding of Monodepth2).  Nothing is masked inside: the zeros of
+ * out-of-view pixels take part in their neighbours' windows as in the reference, and the caller has `valid` from the warp.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct SfmPhotoErrorDesc {
+  int32_t B, n_img, n_scales;                     /* n_img images per sample, all compared with that sample's one target */
+  int32_t H[SFM_MAX_SCALES], W[SFM_MAX_SCALES];   /* independent per scale (not required to be halvings)                 */
+  float ssim_rate;                                /* alpha in [0,1]; 0 = L1 only (no SSIM code runs), 1 = SSIM only      */
+  const float *img[SFM_MAX_SCALES];               /* (B,n_img,3,h,w) planar: the layout of SfmWarpPyramidDesc.warped,    */
+                                                  /* byte for byte the planar source pyramid (B,3*n_img,h,w)             */
+  const float *tgt[SFM_MAX_SCALES];               /* (B,3,h,w) planar                                                    */
+  float *err[SFM_MAX_SCALES];                     /* fwd: (B,n_img,h,w) overwritten                                      */
+  const float *g_err[SFM_MAX_SCALES];             /* bwd: (B,n_img,h,w)                                                  */
+  float *d_img[SFM_MAX_SCALES];                   /* bwd: (B,n_img,3,h,w) overwritten                                    */
+} SfmPhotoErrorDesc;
+
+/* Forward, one launch: err[s][b, i] as defined above for every scale s < n_scales, image i < n_img and sample b < B.
+ * Reads img and tgt; ignores g_err and d_img. */
+int sfm_photo_error_fwd(const SfmPhotoErrorDesc *d, void *stream);
+
+/* Backward for the upstream gradients g_err[s], one launch:
+ *   kappa_c(p) = (alpha / 3) * g_err(p) * (-1/2) * [0 < (1 - S_c) / 2 < 1]                               (F.clip backward)
+ *   d_img_c(q) = ((1 - alpha) / 3) * g_err(q) * sign(X_c - Y_c)(q)                                       (sign(0) = 0)
+ *              + Pool(kappa * dS/dmu_x)(q) + 2 X_c(q) * Pool(kappa * dS/dE[xx])(q) + Y_c(q) * Pool(kappa * dS/dE[xy])(q)
+ * with the statistics recomputed, not stored.  The target is a constant, as everywhere in this library: it gets no gradient.
+ * No atomics, no workspace: two calls on the same inputs agree bit for bit.
+ * Reads img, tgt and g_err; ignores err. */
+int sfm_photo_error_bwd(const SfmPhotoErrorDesc *d, void *stream);
+
+/* Errors of both calls, checked in this order before any HIP call:
+ *   d NULL -> SFM_ERR_NULL;
+ *   n_img outside 1..SFM_MAX_SRC, n_scales outside 1..SFM_MAX_SCALES, B < 0, any H[s] or W[s] < 3, 3 * H[s] * W[s] >= 2^31, or
+ *     2^31 or more wavefront tiles in all (a grid that would overflow) -> SFM_ERR_SHAPE;
+ *   ssim_rate outside [0,1], or NaN -> SFM_ERR_CONFIG;
+ *   B == 0: nothing more is checked, nothing is launched, 0 is returned (an empty shard's pointers may be NULL);
+ *   a pointer the call reads or writes is NULL -> SFM_ERR_NULL. */
+
+/* ------------------------------------------------------------------------------------------
  * DEVELOPMENT ONLY -- environment variables the library reads ONCE per process (at the first call that needs them; setting them
  * later has no effect).  They move work between wavefronts or pick another kernel for the same arithmetic; none changes a result
  * beyond the summation order of the per-wave partial sums.  Not part of the interface: names and meaning may change.

@@ -1,5 +1,4 @@
-"""ctypes binding of libsfmwarp.so (include/sfmwarp.h, include/sfmwarp_ext.h, include/sfmwarp_intrinsics.h, include/sfmwarp_warp_pyramid.h,
-include/sfmwarp_photo_error.h).  No torch types cross this boundary:
+"""ctypes binding of libsfmwarp.so (include/sfmwarp.h).  No torch types cross this boundary:
 every tensor is handed over as a raw device pointer plus explicit sizes.
 
 The library is REQUIRED: there is no CPU or PyTorch fallback.  If it is missing, importing
@@ -67,7 +66,6 @@ class SfmLossDesc(C.Structure):
 
 
 class SfmWarpPyramidDesc(C.Structure):
-    """include/sfmwarp_warp_pyramid.h"""
     _fields_ = [
         ("B", C.c_int32), ("n_src", C.c_int32), ("n_scales", C.c_int32),
         ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
@@ -79,7 +77,6 @@ class SfmWarpPyramidDesc(C.Structure):
 
 
 class SfmPhotoErrorDesc(C.Structure):
-    """include/sfmwarp_photo_error.h"""
     _fields_ = [
         ("B", C.c_int32), ("n_img", C.c_int32), ("n_scales", C.c_int32),
         ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
@@ -125,33 +122,18 @@ SYMBOLS = {
     "sfm_pyramid_variant": (_I, [_I]),
     "sfm_pyramid_hwc_fwd": (_I, [_FP, C.POINTER(C.c_void_p), _I, _I, _I, _I, _I, _V]),
     "sfm_pyramid_pair_hwc_fwd": (_I, [_FP, _FP, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I, _I, _I, _I, _I, _V]),
-}
-
-# every symbol declared in include/sfmwarp_ext.h (entry points newer than the set above)
-EXT_SYMBOLS = {
+    # the backward of sfm_resize_fwd
     "sfm_resize_bwd": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _FP, _I, _I, _I, _I, _V]),
-}
-
-
-# every symbol declared in include/sfmwarp_intrinsics.h (the gradient with respect to the camera intrinsics)
-INTRINSICS_SYMBOLS = {
+    # the gradient with respect to the camera intrinsics
     "sfm_loss_proj_bwd": (_I, [C.POINTER(SfmLossDesc), _I, _V, _Z, _FP, _FP, _V]),
     "sfm_warp_intrinsics_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
     "sfm_warp_intrinsics_bwd": (_I, [_FP, _FP, _I, _FP, _FP, _FP, _FP, _V, _Z, _I, _I, _I, _I, _V]),
     "sfm_pose_proj_bwd_k": (_I, [_FP, _FP, _FP, _FP, _I, _V]),
-}
-
-
-# every symbol declared in include/sfmwarp_warp_pyramid.h (the differentiable warp of the whole source pyramid)
-WARP_PYRAMID_SYMBOLS = {
+    # the differentiable warp of the whole source pyramid
     "sfm_warp_pyramid_fwd": (_I, [C.POINTER(SfmWarpPyramidDesc), _V]),
     "sfm_warp_pyramid_bwd_workspace_bytes": (_Z, [C.POINTER(SfmWarpPyramidDesc)]),
     "sfm_warp_pyramid_bwd": (_I, [C.POINTER(SfmWarpPyramidDesc), _V, _Z, _V]),
-}
-
-
-# every symbol declared in include/sfmwarp_photo_error.h (the per-pixel L1 + SSIM error maps of a warped pyramid)
-PHOTO_ERROR_SYMBOLS = {
+    # the per-pixel L1 + SSIM error maps of a warped pyramid
     "sfm_photo_error_fwd": (_I, [C.POINTER(SfmPhotoErrorDesc), _V]),
     "sfm_photo_error_bwd": (_I, [C.POINTER(SfmPhotoErrorDesc), _V]),
 }
@@ -167,8 +149,7 @@ def _load():
             "libsfmwarp.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(INTRINSICS_SYMBOLS.items()) \
-            + list(WARP_PYRAMID_SYMBOLS.items()) + list(PHOTO_ERROR_SYMBOLS.items()):
+    for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

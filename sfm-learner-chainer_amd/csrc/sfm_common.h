@@ -15,6 +15,36 @@ void set_error(const char* fmt, ...);
 int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
 
+#define SFM_REQUIRE(cond, code, ...) \
+  do {                               \
+    if (!(cond)) return fail(code, __VA_ARGS__); \
+  } while (0)
+
+// The shape checks sfm_warp_pyramid_* and sfm_photo_error_* share, in the order include/sfmwarp.h states them: the per-sample
+// count of the descriptor (`count_name`: "n_src" / "n_img"), n_scales, B, then per scale the frame and the running number of launch
+// units.  units(s, H, W): the units of ONE sample at scale s (the caller may record its own per-scale counts there); `unit` names
+// them in the message, `note` follows the number.  Fills H, W and begin: begin[s] is the first unit of scale s, begin[n_scales]
+// the size of the grid.  The caller goes on with its setting, the empty batch (B == 0 returns before the pointers) and its pointers.
+template <class Units>
+inline int check_pyramid_shape(const char* who, const int B, const int count, const char* count_name, const int n_scales,
+                               const int32_t* dH, const int32_t* dW, const char* unit, const char* note, Units units, int* H, int* W,
+                               int* begin) {
+  SFM_REQUIRE(count >= 1 && count <= SFM_MAX_SRC, SFM_ERR_SHAPE, "%s: %s=%d, need 1..%d", who, count_name, count, SFM_MAX_SRC);
+  SFM_REQUIRE(n_scales >= 1 && n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "%s: n_scales=%d, need 1..%d", who, n_scales, SFM_MAX_SCALES);
+  SFM_REQUIRE(B >= 0, SFM_ERR_SHAPE, "%s: B=%d", who, B);
+  long long total = 0;
+  begin[0] = 0;
+  for (int s = 0; s < n_scales; ++s) {
+    SFM_REQUIRE(dH[s] >= 3 && dW[s] >= 3, SFM_ERR_SHAPE, "%s: scale %d: H=%d W=%d, need H,W >= 3", who, s, dH[s], dW[s]);
+    SFM_REQUIRE(3ll * dH[s] * dW[s] < (1ll << 31), SFM_ERR_SHAPE, "%s: scale %d: 3*H*W too large", who, s);
+    H[s] = dH[s], W[s] = dW[s];
+    total += (long long)B * units(s, H[s], W[s]);
+    SFM_REQUIRE(total < (1ll << 31), SFM_ERR_SHAPE, "%s: too many %s (%lld)%s", who, unit, total, note);
+    begin[s + 1] = (int)total;
+  }
+  return SFM_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // Geometry of one (sample, scale, source): everything the per-pixel projection needs,
 // 32 floats so that a wave fetches it with scalar loads.

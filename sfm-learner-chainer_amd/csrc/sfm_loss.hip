@@ -24,7 +24,6 @@
 #include <hip/hip_ext.h>
 
 #include "sfm_loss_kernels.h"
-#include "sfmwarp_intrinsics.h"
 
 namespace sfm {
 

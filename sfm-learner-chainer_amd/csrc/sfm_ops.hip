@@ -7,13 +7,6 @@
 
 #include "sfm_common.h"
 #include "sfm_warp_pixel.h"
-#include "sfmwarp_ext.h"
-#include "sfmwarp_intrinsics.h"
-
-#define SFM_REQUIRE(cond, code, ...) \
-  do {                               \
-    if (!(cond)) return fail(code, __VA_ARGS__); \
-  } while (0)
 
 namespace sfm {
 

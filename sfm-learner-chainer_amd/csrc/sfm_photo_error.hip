@@ -1,4 +1,4 @@
-// The per-pixel photometric error maps of a whole warped pyramid (include/sfmwarp_photo_error.h): alpha * SSIM + (1 - alpha) * L1 of
+// The per-pixel photometric error maps of a whole warped pyramid (include/sfmwarp.h): alpha * SSIM + (1 - alpha) * L1 of
 // every (scale, sample, image) in ONE launch, its gradient with respect to the images in ONE launch.  No workspace, no atomics, no
 // LDS: every output element is written once by one lane, in a fixed evaluation order.  gfx950 only.
 //
@@ -17,12 +17,6 @@
 // one rounding per term less than dividing each sum first.
 #include "sfm_common.h"
 #include "sfm_warp_pixel.h"
-#include "sfmwarp_photo_error.h"
-
-#define SFM_REQUIRE(cond, code, ...) \
-  do {                               \
-    if (!(cond)) return fail(code, __VA_ARGS__); \
-  } while (0)
 
 namespace sfm {
 
@@ -286,25 +280,16 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_bwd_kernel(const PhotoErrA
 // What both calls check and fill in, in the order the header states.  bwd: the pointers of the backward, else those of the forward.
 static int photo_err_setup(PhotoErrArgs& A, const char* who, const SfmPhotoErrorDesc* d, const bool bwd) {
   SFM_REQUIRE(d, SFM_ERR_NULL, "%s: NULL descriptor", who);
-  SFM_REQUIRE(d->n_img >= 1 && d->n_img <= SFM_MAX_SRC, SFM_ERR_SHAPE, "%s: n_img=%d, need 1..%d", who, d->n_img, SFM_MAX_SRC);
-  SFM_REQUIRE(d->n_scales >= 1 && d->n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "%s: n_scales=%d, need 1..%d", who, d->n_scales,
-              SFM_MAX_SCALES);
-  SFM_REQUIRE(d->B >= 0, SFM_ERR_SHAPE, "%s: B=%d", who, d->B);
-  A.B = d->B, A.n_img = d->n_img, A.n_scales = d->n_scales;
   const int strip = bwd ? PE_BWD_STRIP : PE_FWD_STRIP;
-  long long tiles = 0;
-  A.begin[0] = 0;
-  for (int s = 0; s < d->n_scales; ++s) {
-    const int H = d->H[s], W = d->W[s];
-    SFM_REQUIRE(H >= 3 && W >= 3, SFM_ERR_SHAPE, "%s: scale %d: H=%d W=%d, need H,W >= 3", who, s, H, W);
-    SFM_REQUIRE(3ll * H * W < (1ll << 31), SFM_ERR_SHAPE, "%s: scale %d: 3*H*W too large", who, s);
-    A.H[s] = H, A.W[s] = W;
+  const auto tiles = [&A, d, strip](const int s, const int H, const int W) {
     A.nstrip[s] = (W + strip - 1) / strip;
     A.nchunk[s] = (H + PE_ROWS - 1) / PE_ROWS;
-    tiles += (long long)d->B * d->n_img * A.nstrip[s] * A.nchunk[s];
-    SFM_REQUIRE(tiles < (1ll << 31), SFM_ERR_SHAPE, "%s: too many wavefront tiles (%lld): the grid would overflow", who, tiles);
-    A.begin[s + 1] = (int)tiles;
-  }
+    return (long long)d->n_img * A.nstrip[s] * A.nchunk[s];
+  };
+  if (int e = check_pyramid_shape(who, d->B, d->n_img, "n_img", d->n_scales, d->H, d->W, "wavefront tiles", ": the grid would overflow",
+                                  tiles, A.H, A.W, A.begin))
+    return e;
+  A.B = d->B, A.n_img = d->n_img, A.n_scales = d->n_scales;
   SFM_REQUIRE(d->ssim_rate >= 0.f && d->ssim_rate <= 1.f, SFM_ERR_CONFIG, "%s: ssim_rate=%g, need 0 <= ssim_rate <= 1", who,
               (double)d->ssim_rate);
   A.w_l1 = (1.f - d->ssim_rate) / 3.f;

@@ -1,4 +1,4 @@
-// The differentiable warp of the whole source pyramid of one step (include/sfmwarp_warp_pyramid.h): every scale and every source
+// The differentiable warp of the whole source pyramid of one step (include/sfmwarp.h): every scale and every source
 // warped in ONE launch, differentiated in ONE launch plus a fold of one wavefront per (sample, source).  Per pixel it is the code of
 // sfm_warp_fwd / sfm_warp_bwd (sfm_warp_pixel.h: the reference's own evaluation order), so the values are those operators' bit for
 // bit.  gfx950 only.
@@ -8,12 +8,6 @@
 // its disparity once and loops over the sources.
 #include "sfm_common.h"
 #include "sfm_warp_pixel.h"
-#include "sfmwarp_warp_pyramid.h"
-
-#define SFM_REQUIRE(cond, code, ...) \
-  do {                               \
-    if (!(cond)) return fail(code, __VA_ARGS__); \
-  } while (0)
 
 namespace sfm {
 
@@ -169,23 +163,10 @@ __global__ void __launch_bounds__(64) warp_pyr_fold_kernel(const WarpPyrArgs A) 
 // What both calls check and fill in, in the order the header states.  bwd: the pointers of the backward, else those of the forward.
 static int warp_pyr_setup(WarpPyrArgs& A, const char* who, const SfmWarpPyramidDesc* d, const bool bwd) {
   SFM_REQUIRE(d, SFM_ERR_NULL, "%s: NULL descriptor", who);
-  SFM_REQUIRE(d->n_src >= 1 && d->n_src <= SFM_MAX_SRC, SFM_ERR_SHAPE, "%s: n_src=%d, need 1..%d", who, d->n_src, SFM_MAX_SRC);
-  SFM_REQUIRE(d->n_scales >= 1 && d->n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "%s: n_scales=%d, need 1..%d", who, d->n_scales,
-              SFM_MAX_SCALES);
-  SFM_REQUIRE(d->B >= 0, SFM_ERR_SHAPE, "%s: B=%d", who, d->B);
+  const auto blocks = [&A](const int s, const int H, const int W) { return (long long)(A.nblk[s] = (H * W + WP_BLOCK - 1) / WP_BLOCK); };
+  if (int e = check_pyramid_shape(who, d->B, d->n_src, "n_src", d->n_scales, d->H, d->W, "256-pixel blocks", "", blocks, A.H, A.W, A.begin))
+    return e;
   A.B = d->B, A.n_src = d->n_src, A.n_scales = d->n_scales;
-  long long blocks = 0;
-  A.begin[0] = 0;
-  for (int s = 0; s < d->n_scales; ++s) {
-    const int H = d->H[s], W = d->W[s];
-    SFM_REQUIRE(H >= 3 && W >= 3, SFM_ERR_SHAPE, "%s: scale %d: H=%d W=%d, need H,W >= 3", who, s, H, W);
-    SFM_REQUIRE(3ll * H * W < (1ll << 31), SFM_ERR_SHAPE, "%s: scale %d: 3*H*W too large", who, s);
-    A.H[s] = H, A.W[s] = W;
-    A.nblk[s] = (H * W + WP_BLOCK - 1) / WP_BLOCK;
-    blocks += (long long)d->B * A.nblk[s];
-    SFM_REQUIRE(blocks < (1ll << 31), SFM_ERR_SHAPE, "%s: too many 256-pixel blocks (%lld)", who, blocks);
-    A.begin[s + 1] = (int)blocks;
-  }
   SFM_REQUIRE(d->image_layout == SFM_LAYOUT_PLANAR || d->image_layout == SFM_LAYOUT_HWC, SFM_ERR_CONFIG, "%s: image_layout=%d", who,
               d->image_layout);
   if (d->B == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL

@@ -356,16 +356,28 @@ def layout_for(H, W):
     return "hwc" if H * W < HWC_MAX_PIXELS else "planar"
 
 
+def _set_scales(d, hw):
+    """n_scales, H[] and W[] of any of the three descriptors from hw = [(h, w) of each scale]"""
+    d.n_scales = len(hw)
+    for s, (h, w) in enumerate(hw):
+        d.H[s], d.W[s] = h, w
+
+
+def _one_device(dev, arrays):
+    for t in arrays:
+        if t.device != dev:
+            raise TypeError("every array must live on %s, one is on %s" % (dev, t.device))
+
+
 def loss_desc(B, norm_B, n_src, hw, settings, layout):
     """An SfmLossDesc with every non-pointer field set.  hw: (h, w) of each scale; settings: (smooth_reg, exp_reg, ssim_rate,
     smooth_mode, projection), the last two as _lib.SMOOTH_* / _lib.SFM_PROJECTION_*; layout: "planar" or "hwc".  (Whether
     there are explainability masks shows in the pointers alone.)"""
     d = SfmLossDesc()
-    d.B, d.norm_B, d.n_src, d.n_scales = B, norm_B, n_src, len(hw)
+    d.B, d.norm_B, d.n_src = B, norm_B, n_src
     d.smooth_reg, d.exp_reg, d.ssim_rate, d.smooth_mode, d.projection = settings
     d.image_layout = _LAYOUTS[layout]
-    for s, (h, w) in enumerate(hw):
-        d.H[s], d.W[s] = h, w
+    _set_scales(d, hw)
     return d
 
 
@@ -436,7 +448,7 @@ def _place_workspace(ws, nbytes, device):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the warp of the whole source pyramid (include/sfmwarp_warp_pyramid.h)
+# the warp of the whole source pyramid (include/sfmwarp.h)
 # ---------------------------------------------------------------------------------------------------------------------------
 def _warp_pyramid_desc(src_pyr, disps, poses, K, layout):
     """(descriptor with the inputs bound, the arrays it points at, B, n_src, [(h, w)], device) for warp_pyramid_fwd / _bwd"""
@@ -461,13 +473,10 @@ def _warp_pyramid_desc(src_pyr, disps, poses, K, layout):
     for i, t in enumerate(poses):
         if tuple(t.shape) != (B, 6):
             raise TypeError("poses[%d] must be (B,6)" % i)
-    for t in src_pyr + disps + poses + [K]:
-        if t.device != dev:
-            raise TypeError("every array must live on %s, one is on %s" % (dev, t.device))
+    _one_device(dev, src_pyr + disps + poses + [K])
     d = SfmWarpPyramidDesc()
-    d.B, d.n_src, d.n_scales, d.image_layout = B, n_src, S, _LAYOUTS[layout]
-    for s, (h, w) in enumerate(hw):
-        d.H[s], d.W[s] = h, w
+    d.B, d.n_src, d.image_layout = B, n_src, _LAYOUTS[layout]
+    _set_scales(d, hw)
     d.intrinsics = K.data_ptr()
     for field, arrays in ((d.src, src_pyr), (d.disp, disps), (d.pose, poses)):
         _point(field, arrays)
@@ -512,7 +521,7 @@ def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the per-pixel photometric error maps of a warped pyramid (include/sfmwarp_photo_error.h)
+# the per-pixel photometric error maps of a warped pyramid (include/sfmwarp.h)
 # ---------------------------------------------------------------------------------------------------------------------------
 def _photo_error_desc(imgs, tgts, ssim_rate):
     """(descriptor with the inputs bound, the arrays it points at, B, n_img, [(h, w)], device) for photo_error_fwd / _bwd"""
@@ -531,13 +540,10 @@ def _photo_error_desc(imgs, tgts, ssim_rate):
         if tuple(imgs[s].shape) != (B, n_img, 3, h, w) or tuple(tgts[s].shape) != (B, 3, h, w):
             raise TypeError("scale %d: expected imgs (B,n_img,3,h,w) = %s and tgts (B,3,h,w), got %s and %s"
                             % (s, (B, n_img, 3, h, w), tuple(imgs[s].shape), tuple(tgts[s].shape)))
-    for t in imgs + tgts:
-        if t.device != dev:
-            raise TypeError("every array must live on %s, one is on %s" % (dev, t.device))
+    _one_device(dev, imgs + tgts)
     d = SfmPhotoErrorDesc()
-    d.B, d.n_img, d.n_scales, d.ssim_rate = B, n_img, S, float(ssim_rate)
-    for s, (h, w) in enumerate(hw):
-        d.H[s], d.W[s] = h, w
+    d.B, d.n_img, d.ssim_rate = B, n_img, float(ssim_rate)
+    _set_scales(d, hw)
     for field, arrays in ((d.img, imgs), (d.tgt, tgts)):
         _point(field, arrays)
     return d, (imgs, tgts), B, n_img, hw, dev

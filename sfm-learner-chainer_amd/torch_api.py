@@ -361,6 +361,57 @@ def _poses(pred_poses, B, n_src):
     return out
 
 
+def _masks(pred_maskes, B, n_src, H, W, S):
+    """The explainability logits of a loss with exp_reg > 0: S arrays (B,n_src,H>>s,W>>s) -> float32, contiguous"""
+    if pred_maskes is None or len(pred_maskes) != S:
+        raise ValueError("exp_reg > 0 needs the explainability logits (pred_maskes), one per scale")
+    masks = []
+    for s, t in enumerate(pred_maskes):
+        t = _dev_float(t, "pred_maskes[%d]" % s, 4)
+        if tuple(t.shape) != (B, n_src, H >> s, W >> s):
+            raise TypeError("pred_maskes[%d] must be (B,n_src,H>>%d,W>>%d), got %s" % (s, s, s, tuple(t.shape)))
+        masks.append(t)
+    return masks
+
+
+def _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt=None, exp_reg=0.0, pred_maskes=None):
+    """The inputs of `sfm_learner_loss` (which passes `tgt`, its checked target frames) and of `warp_pyramid` (which does not, and
+    takes the intrinsics as constants), checked in the one order both have: src_imgs (B,n_src,3,H,W) -- with `tgt`, that it is
+    (B,3,H,W) too --, 1..8 sources, 1..8 scales, intrinsics (B,S,3,3), pred_disps[s] (B,1,H>>s,W>>s), the poses, with exp_reg > 0
+    the masks, and last that every array lives on the frames' device.  -> (src, K, disps, poses, masks)"""
+    src = ops._dev(src_imgs, "src_imgs", 5)
+    B, n_src, c, H, W = src.shape
+    if tgt is None:
+        if c != 3:
+            raise TypeError("src_imgs must be (B,n_src,3,H,W), got %s" % (tuple(src.shape),))
+    elif tuple(tgt.shape) != (B, 3, H, W) or c != 3:
+        raise TypeError("tgt_img must be (B,3,H,W) and src_imgs (B,n_src,3,H,W), got %s and %s" % (tuple(tgt.shape), tuple(src.shape)))
+    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d source images, got %d" % (_lib.SFM_MAX_SRC, n_src))
+    S = len(pred_disps)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
+    K = ops._dev(intrinsics, "intrinsics", 4)
+    if tuple(K.shape) != (B, S, 3, 3):
+        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
+    if tgt is None and K.requires_grad:
+        raise TypeError("warp_pyramid does not differentiate the intrinsics: detach them, or warp per (scale, source) with "
+                        "projective_inverse_warp, which returns their gradient")
+    disps = []
+    for s, t in enumerate(pred_disps):
+        t = _dev_float(t, "pred_disps[%d]" % s, 4)
+        if tuple(t.shape) != (B, 1, H >> s, W >> s):
+            raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s, got %s" % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
+        disps.append(t)
+    poses = _poses(pred_poses, B, n_src)
+    masks = _masks(pred_maskes, B, n_src, H, W, S) if exp_reg > 0 else []
+    dev = src.device if tgt is None else tgt.device
+    for t in [K] + disps + poses + masks:
+        if t.device != dev:
+            raise TypeError("every array must live on %s, one is on %s" % (dev, t.device))
+    return src, K, disps, poses, masks
+
+
 def sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred_maskes=None, *, smooth_reg, exp_reg=0.,
                      ssim_rate=0., smooth_mode="second_order", projection="fast", norm_batch=None):
     """The loss of SFMLearner.__call__ (models/base_model.py:48-124) with torch.autograd gradients.
@@ -385,38 +436,10 @@ def sfm_learner_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, pred
     Gradients are per call: several forwards before one backward each keep their own."""
     smooth_mode, projection = _lib.smooth_mode_id(smooth_mode), _lib.projection_id(projection)
     tgt = ops._dev(tgt_img, "tgt_img", 4)
-    src = ops._dev(src_imgs, "src_imgs", 5)
-    B, n_src, c, H, W = src.shape
-    if tuple(tgt.shape) != (B, 3, H, W) or c != 3:
-        raise TypeError("tgt_img must be (B,3,H,W) and src_imgs (B,n_src,3,H,W), got %s and %s" % (tuple(tgt.shape), tuple(src.shape)))
-    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
-        raise TypeError("1..%d source images, got %d" % (_lib.SFM_MAX_SRC, n_src))
-    S = len(pred_disps)
-    if not 1 <= S <= _lib.SFM_MAX_SCALES:
-        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
-    K = ops._dev(intrinsics, "intrinsics", 4)
-    if tuple(K.shape) != (B, S, 3, 3):
-        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
-    disps = []
-    for s, t in enumerate(pred_disps):
-        t = _dev_float(t, "pred_disps[%d]" % s, 4)
-        if tuple(t.shape) != (B, 1, H >> s, W >> s):
-            raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s, got %s" % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
-        disps.append(t)
-    poses = _poses(pred_poses, B, n_src)
     exp_reg = float(exp_reg or 0.0)
-    masks = []
-    if exp_reg > 0:
-        if pred_maskes is None or len(pred_maskes) != S:
-            raise ValueError("exp_reg > 0 needs the explainability logits (pred_maskes), one per scale")
-        for s, t in enumerate(pred_maskes):
-            t = _dev_float(t, "pred_maskes[%d]" % s, 4)
-            if tuple(t.shape) != (B, n_src, H >> s, W >> s):
-                raise TypeError("pred_maskes[%d] must be (B,n_src,H>>%d,W>>%d), got %s" % (s, s, s, tuple(t.shape)))
-            masks.append(t)
-    for t in [K] + disps + poses + masks:
-        if t.device != tgt.device:
-            raise TypeError("every array must live on %s, one is on %s" % (tgt.device, t.device))
+    src, K, disps, poses, masks = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt, exp_reg, pred_maskes)
+    B, n_src, _, H, W = src.shape
+    S = len(disps)
     grad = torch.is_grad_enabled() and any(t.requires_grad for t in disps + poses + masks)
     grad_k = grad and K.requires_grad
     cfg = (float(smooth_reg or 0.0), exp_reg, float(ssim_rate or 0.0), smooth_mode, projection,
@@ -532,31 +555,9 @@ def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=F
 
     Two launches forward (the source pyramid, the warp of all scales and sources); backward one launch over the pixels plus a small
     fold, whatever S and n_src are.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture."""
-    src = ops._dev(src_imgs, "src_imgs", 5)
-    B, n_src, c, H, W = src.shape
-    if c != 3:
-        raise TypeError("src_imgs must be (B,n_src,3,H,W), got %s" % (tuple(src.shape),))
-    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
-        raise TypeError("1..%d source images, got %d" % (_lib.SFM_MAX_SRC, n_src))
-    S = len(pred_disps)
-    if not 1 <= S <= _lib.SFM_MAX_SCALES:
-        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
-    K = ops._dev(intrinsics, "intrinsics", 4)
-    if tuple(K.shape) != (B, S, 3, 3):
-        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
-    if K.requires_grad:
-        raise TypeError("warp_pyramid does not differentiate the intrinsics: detach them, or warp per (scale, source) with "
-                        "projective_inverse_warp, which returns their gradient")
-    disps = []
-    for s, t in enumerate(pred_disps):
-        t = _dev_float(t, "pred_disps[%d]" % s, 4)
-        if tuple(t.shape) != (B, 1, H >> s, W >> s):
-            raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s, got %s" % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
-        disps.append(t)
-    poses = _poses(pred_poses, B, n_src)
-    for t in [K] + disps + poses:
-        if t.device != src.device:
-            raise TypeError("every array must live on %s, one is on %s" % (src.device, t.device))
+    src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses)
+    B, n_src, _, H, W = src.shape
+    S = len(disps)
     out = _WarpPyramid.apply(src.view(B, 3 * n_src, H, W), K, S, bool(return_valid), *disps, *poses)
     return (list(out[:S]), list(out[S:])) if return_valid else list(out)
 

@@ -298,6 +298,244 @@ def cases():
     add("augment_images: ndim 4", lambda: augment.augment_images(T(2, 9, 8, 8), P))
     add("augment_images: float16", lambda: augment.augment_images(T(2, 3, 3, 8, 8, dtype=torch.float16), P))
     add("augment_images: not a tensor", lambda: augment.augment_images(np.zeros((2, 3, 3, 8, 8), np.float32), P))
+    return out + _newer_cases()
+
+
+def _newer_cases():
+    """The refusals of the entry points added after the table was first written (rows are only ever appended)"""
+    out = []
+    add = lambda label, fn: out.append((label, fn))
+    F64, I32, F16, CPU, DEV1 = dict(dtype=torch.float64), dict(dtype=torch.int32), dict(dtype=torch.float16), dict(device="cpu"), \
+        dict(device="cuda:1")
+
+    # torch_api.warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses): the inputs of the loss without tgt_img
+    def wp(a, **kw):
+        return ta.warp_pyramid(*a[1:], **kw)
+    A = _loss_args
+    add("warp_pyramid: cpu", lambda: wp(A(device="cpu")))
+    add("warp_pyramid: src_imgs not a tensor", lambda: wp(_with(A(), 1, None)))
+    add("warp_pyramid: src_imgs stacked", lambda: wp(_with(A(), 1, T(2, 6, 16, 24))))
+    add("warp_pyramid: src_imgs float64", lambda: wp(_with(A(), 1, T(2, 2, 3, 16, 24, **F64))))
+    add("warp_pyramid: src_imgs of 4 channels", lambda: wp(_with(A(), 1, T(2, 2, 4, 16, 24))))
+    add("warp_pyramid: src_imgs of 4 channels, 9 scales", lambda: wp(_with(A(H=1024, W=1024, S=9), 1, T(2, 2, 4, 1024, 1024))))
+    add("warp_pyramid: no sources", lambda: wp(_with(_with(A(), 1, T(2, 0, 3, 16, 24)), 4, [])))
+    add("warp_pyramid: 8 sources, one pose short", lambda: wp(_with(A(n=8), 4, [T(2, 6)] * 7)))
+    add("warp_pyramid: 9 sources", lambda: wp(A(n=9)))
+    add("warp_pyramid: 9 sources, no scales", lambda: wp(_with(A(n=9), 3, [])))
+    add("warp_pyramid: no scales", lambda: wp(_with(A(), 3, [])))
+    add("warp_pyramid: 9 scales", lambda: wp(A(H=1024, W=1024, S=9)))
+    add("warp_pyramid: 9 scales, intrinsics cpu", lambda: wp(_with(A(H=1024, W=1024, S=9), 2, T(2, 9, 3, 3, **CPU))))
+    add("warp_pyramid: intrinsics cpu", lambda: wp(_with(A(), 2, T(2, 2, 3, 3, **CPU))))
+    add("warp_pyramid: intrinsics of one scale", lambda: wp(_with(A(), 2, T(2, 1, 3, 3))))
+    add("warp_pyramid: intrinsics of another B", lambda: wp(_with(A(), 2, T(1, 2, 3, 3))))
+    add("warp_pyramid: intrinsics ndim", lambda: wp(_with(A(), 2, T(2, 3, 3))))
+    add("warp_pyramid: intrinsics float16", lambda: wp(_with(A(), 2, T(2, 2, 3, 3, **F16))))
+    add("warp_pyramid: intrinsics require grad", lambda: wp(_with(A(), 2, T(2, 2, 3, 3).requires_grad_())))
+    add("warp_pyramid: intrinsics of one scale require grad", lambda: wp(_with(A(), 2, T(2, 1, 3, 3).requires_grad_())))
+    add("warp_pyramid: intrinsics require grad, pred_disps[0] cpu",
+        lambda: wp(_with(_with(A(), 2, T(2, 2, 3, 3).requires_grad_()), 3, [T(2, 1, 16, 24, **CPU), T(2, 1, 8, 12)])))
+    add("warp_pyramid: pred_disps[1] of scale 0", lambda: wp(_with(A(), 3, [T(2, 1, 16, 24), T(2, 1, 16, 24)])))
+    add("warp_pyramid: pred_disps[0] of 2 channels", lambda: wp(_with(A(), 3, [T(2, 2, 16, 24), T(2, 1, 8, 12)])))
+    add("warp_pyramid: pred_disps[1] float64", lambda: wp(_with(A(), 3, [T(2, 1, 16, 24), T(2, 1, 8, 12, **F64)])))
+    add("warp_pyramid: pred_disps[1] ndim", lambda: wp(_with(A(), 3, [T(2, 1, 16, 24), T(2, 8, 12)])))
+    add("warp_pyramid: pred_disps[0] cpu", lambda: wp(_with(A(), 3, [T(2, 1, 16, 24, **CPU), T(2, 1, 8, 12)])))
+    add("warp_pyramid: pred_disps[0] not a tensor", lambda: wp(_with(A(), 3, [1.0, T(2, 1, 8, 12)])))
+    add("warp_pyramid: pred_disps[1] of scale 0, one pose short", lambda: wp(_with(_with(A(), 3, [T(2, 1, 16, 24)] * 2), 4, [T(2, 6)])))
+    add("warp_pyramid: one pose short", lambda: wp(_with(A(), 4, [T(2, 6)])))
+    add("warp_pyramid: pred_poses[1] (B,5)", lambda: wp(_with(A(), 4, [T(2, 6), T(2, 5)])))
+    add("warp_pyramid: pred_poses[0] ndim", lambda: wp(_with(A(), 4, [T(12), T(2, 6)])))
+    add("warp_pyramid: pred_poses[1] int32", lambda: wp(_with(A(), 4, [T(2, 6), T(2, 6, **I32)])))
+    add("warp_pyramid: packed poses of 3 sources", lambda: wp(_with(A(), 4, T(2, 18))))
+    add("warp_pyramid: packed poses ndim", lambda: wp(_with(A(), 4, T(2, 2, 6))))
+    add("warp_pyramid: packed poses cpu", lambda: wp(_with(A(), 4, T(2, 12, **CPU))))
+    add("warp_pyramid: intrinsics on another device", lambda: wp(_with(A(), 2, T(2, 2, 3, 3, **DEV1))))
+    add("warp_pyramid: pred_disps[1] on another device", lambda: wp(_with(A(), 3, [T(2, 1, 16, 24), T(2, 1, 8, 12, **DEV1)])))
+    add("warp_pyramid: pred_poses[0] on another device", lambda: wp(_with(A(), 4, [T(2, 6, **DEV1), T(2, 6)])))
+    add("warp_pyramid: pred_poses[1] (B,5), intrinsics on another device",
+        lambda: wp(_with(_with(A(), 2, T(2, 2, 3, 3, **DEV1)), 4, [T(2, 6), T(2, 5)])))
+    # ... and the order of the same checks inside the loss, where the masks come before the device
+    L = lambda a, **kw: ta.sfm_learner_loss(*a, **dict(dict(smooth_reg=0.1), **kw))
+    add("loss: intrinsics on another device", lambda: L(_with(A(), 2, T(2, 2, 3, 3, **DEV1))))
+    add("loss: pred_disps[0] on another device", lambda: L(_with(A(), 3, [T(2, 1, 16, 24, **DEV1), T(2, 1, 8, 12)])))
+    add("loss: pred_poses[1] on another device", lambda: L(_with(A(), 4, [T(2, 6), T(2, 6, **DEV1)])))
+    add("loss: pred_maskes[1] on another device", lambda: L(A() + [[T(2, 2, 16, 24), T(2, 2, 8, 12, **DEV1)]], exp_reg=0.2))
+    add("loss: intrinsics on another device, pred_maskes[1] of 1 source",
+        lambda: L(_with(A(), 2, T(2, 2, 3, 3, **DEV1)) + [[T(2, 2, 16, 24), T(2, 1, 8, 12)]], exp_reg=0.2))
+    add("loss: intrinsics on another device, exp_reg without masks", lambda: L(_with(A(), 2, T(2, 2, 3, 3, **DEV1)), exp_reg=0.2))
+    add("loss: src_imgs of 4 channels, 9 scales", lambda: L(_with(A(H=1024, W=1024, S=9), 1, T(2, 2, 4, 1024, 1024))))
+    add("loss: 9 sources, no scales", lambda: L(_with(A(n=9), 3, [])))
+    add("loss: 9 scales, intrinsics cpu", lambda: L(_with(A(H=1024, W=1024, S=9), 2, T(2, 9, 3, 3, **CPU))))
+    add("loss: intrinsics of one scale, pred_disps[0] cpu", lambda: L(_with(_with(A(), 2, T(2, 1, 3, 3)), 3, [T(2, 1, 16, 24, **CPU), T(2, 1, 8, 12)])))
+    add("loss: pred_disps[1] of scale 0, one pose short", lambda: L(_with(_with(A(), 3, [T(2, 1, 16, 24)] * 2), 4, [T(2, 6)])))
+    add("loss: one pose short, exp_reg without masks", lambda: L(_with(A(), 4, [T(2, 6)]), exp_reg=0.2))
+
+    # torch_api.photometric_error(imgs, tgt, ssim_rate=): a single tgt is turned into its pyramid by a launch, so only what is
+    # checked before that is reachable; a list of targets reaches every check
+    pe = lambda imgs, tgt: ta.photometric_error(imgs, tgt, ssim_rate=0.15)
+    X = lambda B=2, n=2, H=16, W=24, S=2, **kw: [T(B, n, 3, H >> s, W >> s, **kw) for s in range(S)]
+    Y = lambda B=2, H=16, W=24, S=2, **kw: [T(B, 3, H >> s, W >> s, **kw) for s in range(S)]
+    add("photometric_error: imgs a tensor", lambda: pe(T(2, 2, 3, 16, 24), Y()))
+    add("photometric_error: no scales", lambda: pe([], []))
+    add("photometric_error: 9 scales", lambda: pe(X(H=1024, W=1024, S=9), Y(H=1024, W=1024, S=9)))
+    add("photometric_error: imgs[0] cpu", lambda: pe(X(**CPU), Y()))
+    add("photometric_error: imgs[1] float64", lambda: pe([X()[0], T(2, 2, 3, 8, 12, **F64)], Y()))
+    add("photometric_error: imgs[1] int32", lambda: pe([X()[0], T(2, 2, 3, 8, 12, **I32)], Y()))
+    add("photometric_error: imgs[0] ndim", lambda: pe([T(2, 6, 16, 24), X()[1]], Y()))
+    add("photometric_error: imgs[0] not a tensor", lambda: pe([None, X()[1]], Y()))
+    add("photometric_error: imgs[0] of 4 channels", lambda: pe([T(2, 2, 4, 16, 24), X()[1]], Y()))
+    add("photometric_error: imgs[1] of another B", lambda: pe([X()[0], T(1, 2, 3, 8, 12)], Y()))
+    add("photometric_error: imgs[1] of another n", lambda: pe([X()[0], T(2, 3, 3, 8, 12)], Y()))
+    add("photometric_error: no images", lambda: pe(X(n=0), Y()))
+    add("photometric_error: 9 images", lambda: pe(X(n=9), Y()))
+    add("photometric_error: 9 images, one tgt short", lambda: pe(X(n=9), Y()[:1]))
+    add("photometric_error: one tgt short", lambda: pe(X(), Y()[:1]))
+    add("photometric_error: tgt[1] cpu", lambda: pe(X(), [Y()[0], T(2, 3, 8, 12, **CPU)]))
+    add("photometric_error: tgt[0] float64", lambda: pe(X(), [T(2, 3, 16, 24, **F64), Y()[1]]))
+    add("photometric_error: tgt[1] ndim", lambda: pe(X(), [Y()[0], T(2, 1, 3, 8, 12)]))
+    add("photometric_error: tgt[1] of scale 0", lambda: pe(X(), [Y()[0], Y()[0]]))
+    add("photometric_error: tgt[0] of another B", lambda: pe(X(), [T(1, 3, 16, 24), Y()[1]]))
+    add("photometric_error: tgt[0] of 1 channel", lambda: pe(X(), [T(2, 1, 16, 24), Y()[1]]))
+    add("photometric_error: imgs[1] on another device", lambda: pe([X()[0], T(2, 2, 3, 8, 12, **DEV1)], Y()))
+    add("photometric_error: tgt[0] on another device", lambda: pe(X(), [T(2, 3, 16, 24, **DEV1), Y()[1]]))
+    add("photometric_error: tgt[0] of 1 channel, tgt[1] on another device", lambda: pe(X(), [T(2, 1, 16, 24), T(2, 3, 8, 12, **DEV1)]))
+    add("photometric_error: single tgt cpu", lambda: pe(X(), T(2, 3, 16, 24, **CPU)))
+    add("photometric_error: single tgt ndim", lambda: pe(X(), T(3, 16, 24)))
+    add("photometric_error: single tgt float16", lambda: pe(X(), T(2, 3, 16, 24, **F16)))
+    add("photometric_error: single tgt of another frame", lambda: pe(X(), T(2, 3, 16, 22)))
+    add("photometric_error: single tgt, imgs[1] of scale 0", lambda: pe([X()[0], X()[0]], T(2, 3, 16, 24)))
+    add("photometric_error: single tgt of another B", lambda: pe(X(), T(1, 3, 16, 24)))
+    add("photometric_error: single tgt of 1 channel", lambda: pe(X(), T(2, 1, 16, 24)))
+    add("photometric_error: single tgt of another frame and B", lambda: pe(X(), T(1, 3, 16, 22)))
+
+    # ops.warp_pyramid_fwd / _bwd(src_pyr, disps, poses, K, layout[, g_warped]): the descriptor builder they share (g_warped is
+    # looked at after the first data_ptr())
+    def P(B=2, H=16, W=24, S=2, n=2, hwc=False):
+        a = _bind_args(B, H, W, S, n, hwc)
+        return [a[1], a[3], a[4], a[2], "hwc" if hwc else "planar"]
+    for name, fn in (("warp_pyramid_fwd", ops.warp_pyramid_fwd), ("warp_pyramid_bwd", lambda *a: ops.warp_pyramid_bwd(*a, [None, None]))):
+        c = lambda label, thunk, name=name: add("%s: %s" % (name, label), thunk)
+        c("layout", lambda fn=fn: fn(*_with(P(), 4, "nhwc")))
+        c("layout None, no scales", lambda fn=fn: fn([], [], P()[2], P()[3], None))
+        c("one src scale short", lambda fn=fn: fn(*_with(P(), 0, P()[0][:1])))
+        c("no scales", lambda fn=fn: fn([], [], P()[2], P()[3], "planar"))
+        c("9 scales", lambda fn=fn: fn(*P(H=1024, W=1024, S=9)))
+        c("no sources", lambda fn=fn: fn(*_with(P(), 2, [])))
+        c("9 sources", lambda fn=fn: fn(*P(n=9)))
+        c("8 sources, 8 scales, src_pyr[7] cpu", lambda fn=fn: fn(*_with(P(H=512, W=512, S=8, n=8), 0, P(H=512, W=512, S=8, n=8)[0][:7] + [T(2, 24, 4, 4, **CPU)])))
+        c("src_pyr[1] cpu", lambda fn=fn: fn(*_with(P(), 0, [T(2, 6, 16, 24), T(2, 6, 8, 12, **CPU)])))
+        c("src_pyr[0] float64", lambda fn=fn: fn(*_with(P(), 0, [T(2, 6, 16, 24, **F64), T(2, 6, 8, 12)])))
+        c("src_pyr planar under hwc", lambda fn=fn: fn(*_with(P(), 4, "hwc")))
+        c("src_pyr hwc under planar", lambda fn=fn: fn(*_with(P(hwc=True), 4, "planar")))
+        c("disps[1] ndim", lambda fn=fn: fn(*_with(P(), 1, [T(2, 1, 16, 24), T(2, 8, 12)])))
+        c("disps[0] not a tensor", lambda fn=fn: fn(*_with(P(), 1, [None, T(2, 1, 8, 12)])))
+        c("poses[1] ndim", lambda fn=fn: fn(*_with(P(), 2, [T(2, 6), T(12)])))
+        c("poses[0] cpu", lambda fn=fn: fn(*_with(P(), 2, [T(2, 6, **CPU), T(2, 6)])))
+        c("poses[0] cpu, intrinsics ndim", lambda fn=fn: fn(*_with(_with(P(), 2, [T(2, 6, **CPU), T(2, 6)]), 3, T(2, 3, 3))))
+        c("intrinsics ndim", lambda fn=fn: fn(*_with(P(), 3, T(2, 3, 3))))
+        c("intrinsics cpu", lambda fn=fn: fn(*_with(P(), 3, T(2, 2, 3, 3, **CPU))))
+        c("intrinsics float64", lambda fn=fn: fn(*_with(P(), 3, T(2, 2, 3, 3, **F64))))
+        c("intrinsics of one scale", lambda fn=fn: fn(*_with(P(), 3, T(2, 1, 3, 3))))
+        c("intrinsics of another B", lambda fn=fn: fn(*_with(P(), 3, T(1, 2, 3, 3))))
+        c("intrinsics of another B, src_pyr[0] of 3 sources", lambda fn=fn: fn(*_with(_with(P(), 3, T(1, 2, 3, 3)), 0, [T(2, 9, 16, 24), T(2, 6, 8, 12)])))
+        c("src_pyr[0] of 3 sources", lambda fn=fn: fn(*_with(P(), 0, [T(2, 9, 16, 24), T(2, 6, 8, 12)])))
+        c("src_pyr[1] of another frame", lambda fn=fn: fn(*_with(P(), 0, [T(2, 6, 16, 24), T(2, 6, 8, 11)])))
+        c("src_pyr[1] of another frame, hwc", lambda fn=fn: fn(*_with(P(hwc=True), 0, [T(2, 2, 16, 24, 3), T(2, 2, 8, 11, 3)])))
+        c("disps[0] of 2 channels", lambda fn=fn: fn(*_with(P(), 1, [T(2, 2, 16, 24), T(2, 1, 8, 12)])))
+        c("disps[1] of another B", lambda fn=fn: fn(*_with(P(), 1, [T(2, 1, 16, 24), T(1, 1, 8, 12)])))
+        c("disps[1] of another B, poses[0] (B,5)", lambda fn=fn: fn(*_with(_with(P(), 1, [T(2, 1, 16, 24), T(1, 1, 8, 12)]), 2, [T(2, 5), T(2, 6)])))
+        c("poses[1] (B,5)", lambda fn=fn: fn(*_with(P(), 2, [T(2, 6), T(2, 5)])))
+        c("poses[0] of another B", lambda fn=fn: fn(*_with(P(), 2, [T(1, 6), T(2, 6)])))
+        c("poses[1] (B,5), src_pyr[1] on another device", lambda fn=fn: fn(*_with(_with(P(), 2, [T(2, 6), T(2, 5)]), 0, [T(2, 6, 16, 24), T(2, 6, 8, 12, **DEV1)])))
+        c("src_pyr[1] on another device", lambda fn=fn: fn(*_with(P(), 0, [T(2, 6, 16, 24), T(2, 6, 8, 12, **DEV1)])))
+        c("disps[0] on another device", lambda fn=fn: fn(*_with(P(), 1, [T(2, 1, 16, 24, **DEV1), T(2, 1, 8, 12)])))
+        c("poses[1] on another device", lambda fn=fn: fn(*_with(P(), 2, [T(2, 6), T(2, 6, **DEV1)])))
+        c("intrinsics on another device", lambda fn=fn: fn(*_with(P(), 3, T(2, 2, 3, 3, **DEV1))))
+
+    # ops.photo_error_fwd / _bwd(imgs, tgts, ssim_rate[, g_err]): likewise
+    for name, fn in (("photo_error_fwd", lambda i, t: ops.photo_error_fwd(i, t, 0.15)), ("photo_error_bwd", lambda i, t: ops.photo_error_bwd(i, t, 0.15, [None, None]))):
+        c = lambda label, thunk, name=name: add("%s: %s" % (name, label), thunk)
+        c("imgs a tensor", lambda fn=fn: fn(T(2, 2, 3, 16, 24), Y()))
+        c("tgts a tensor", lambda fn=fn: fn(X(), T(2, 3, 16, 24)))
+        c("tgts a tensor, no scales", lambda fn=fn: fn([], T(2, 3, 16, 24)))
+        c("one tgt short", lambda fn=fn: fn(X(), Y()[:1]))
+        c("no scales", lambda fn=fn: fn([], []))
+        c("9 scales", lambda fn=fn: fn(X(H=1024, W=1024, S=9), Y(H=1024, W=1024, S=9)))
+        c("9 scales, 8 tgts", lambda fn=fn: fn(X(H=1024, W=1024, S=9), Y(H=1024, W=1024, S=8)))
+        c("8 scales, 8 images, tgts[7] cpu", lambda fn=fn: fn(X(H=512, W=512, S=8, n=8), Y(H=512, W=512, S=7) + [T(2, 3, 4, 4, **CPU)]))
+        c("imgs[1] cpu", lambda fn=fn: fn([X()[0], T(2, 2, 3, 8, 12, **CPU)], Y()))
+        c("imgs[0] float16", lambda fn=fn: fn([T(2, 2, 3, 16, 24, **F16), X()[1]], Y()))
+        c("imgs[0] ndim", lambda fn=fn: fn([T(2, 6, 16, 24), X()[1]], Y()))
+        c("imgs[1] not a tensor", lambda fn=fn: fn([X()[0], None], Y()))
+        c("tgts[0] float64", lambda fn=fn: fn(X(), [T(2, 3, 16, 24, **F64), Y()[1]]))
+        c("tgts[1] ndim", lambda fn=fn: fn(X(), [Y()[0], T(2, 1, 3, 8, 12)]))
+        c("imgs[1] cpu, tgts[0] ndim", lambda fn=fn: fn([X()[0], T(2, 2, 3, 8, 12, **CPU)], [T(6, 16, 24), Y()[1]]))
+        c("no images", lambda fn=fn: fn(X(n=0), Y()))
+        c("9 images", lambda fn=fn: fn(X(n=9), Y()))
+        c("9 images, tgts[0] of another B", lambda fn=fn: fn(X(n=9), [T(1, 3, 16, 24), Y()[1]]))
+        c("imgs[0] of 4 channels", lambda fn=fn: fn([T(2, 2, 4, 16, 24), X()[1]], Y()))
+        c("imgs[1] of another B", lambda fn=fn: fn([X()[0], T(1, 2, 3, 8, 12)], Y()))
+        c("imgs[1] of another n", lambda fn=fn: fn([X()[0], T(2, 3, 3, 8, 12)], Y()))
+        c("tgts[1] of scale 0", lambda fn=fn: fn(X(), [Y()[0], Y()[0]]))
+        c("tgts[0] of another B", lambda fn=fn: fn(X(), [T(1, 3, 16, 24), Y()[1]]))
+        c("tgts[0] of 1 channel", lambda fn=fn: fn(X(), [T(2, 1, 16, 24), Y()[1]]))
+        c("tgts[0] of 1 channel, imgs[1] on another device", lambda fn=fn: fn([X()[0], T(2, 2, 3, 8, 12, **DEV1)], [T(2, 1, 16, 24), Y()[1]]))
+        c("imgs[1] on another device", lambda fn=fn: fn([X()[0], T(2, 2, 3, 8, 12, **DEV1)], Y()))
+        c("tgts[0] on another device", lambda fn=fn: fn(X(), [T(2, 3, 16, 24, **DEV1), Y()[1]]))
+
+    # ops.resize_bwd(gys, in_hw)
+    rb = lambda gys: ops.resize_bwd(gys, (16, 24))
+    add("resize_bwd: no arrays", lambda: rb([]))
+    add("resize_bwd: 9 arrays", lambda: rb([T(1, 3, 8, 8)] * 9))
+    add("resize_bwd: 9 arrays on the cpu", lambda: rb([T(1, 3, 8, 8, **CPU)] * 9))
+    add("resize_bwd: 8 arrays, the last on the cpu", lambda: rb([T(1, 3, 8, 8)] * 7 + [T(1, 3, 8, 8, **CPU)]))
+    add("resize_bwd: one array, cpu", lambda: rb(T(1, 3, 8, 8, **CPU)))
+    add("resize_bwd: one array, ndim", lambda: rb(T(3, 8, 8)))
+    add("resize_bwd: not a tensor", lambda: rb([None]))
+    add("resize_bwd: gys[1] float64", lambda: rb([T(1, 3, 8, 8), T(1, 3, 4, 4, **F64)]))
+    add("resize_bwd: gys[1] bfloat16", lambda: rb([T(1, 3, 8, 8), T(1, 3, 4, 4, dtype=torch.bfloat16)]))
+    add("resize_bwd: gys[0] ndim", lambda: rb([T(3, 8, 8), T(1, 3, 4, 4)]))
+    add("resize_bwd: gys[1] of another N", lambda: rb([T(1, 3, 8, 8), T(2, 3, 4, 4)]))
+    add("resize_bwd: gys[2] of another C", lambda: rb([T(1, 3, 8, 8), T(1, 3, 4, 4), T(1, 1, 2, 2)]))
+    add("resize_bwd: gys[1] on another device", lambda: rb([T(1, 3, 8, 8), T(1, 3, 4, 4, **DEV1)]))
+    add("resize_bwd: gys[1] of another N, gys[2] on another device", lambda: rb([T(1, 3, 8, 8), T(2, 3, 4, 4), T(1, 3, 4, 4, **DEV1)]))
+
+    # ops.warp_bwd_intrinsics(imgs, depth, pose6, K, g_warped): warp_bwd's arguments and checks
+    w = lambda imgs=None, depth=None, pose=None, K=None: [T(2, 3, 8, 8) if imgs is None else imgs, T(2, 64) if depth is None else depth,
+                                                          T(2, 6) if pose is None else pose, T(2, 3, 3) if K is None else K]
+    wk = lambda a, g=None: ops.warp_bwd_intrinsics(*a, T(2, 3, 8, 8) if g is None else g)
+    add("warp_bwd_intrinsics: imgs cpu", lambda: wk(w(imgs=T(2, 3, 8, 8, **CPU))))
+    add("warp_bwd_intrinsics: imgs ndim 3", lambda: wk(w(imgs=T(3, 8, 8))))
+    add("warp_bwd_intrinsics: imgs float64", lambda: wk(w(imgs=T(2, 3, 8, 8, **F64))))
+    add("warp_bwd_intrinsics: depth float64", lambda: wk(w(depth=T(2, 64, **F64))))
+    add("warp_bwd_intrinsics: depth cpu", lambda: wk(w(depth=T(2, 64, **CPU))))
+    add("warp_bwd_intrinsics: depth of 2 rows", lambda: wk(w(depth=T(2, 2, 64))))
+    add("warp_bwd_intrinsics: depth of another frame", lambda: wk(w(depth=T(2, 63))))
+    add("warp_bwd_intrinsics: depth of another frame, poses ndim", lambda: wk(w(depth=T(2, 63), pose=T(12))))
+    add("warp_bwd_intrinsics: poses ndim", lambda: wk(w(pose=T(12))))
+    add("warp_bwd_intrinsics: poses (N,5)", lambda: wk(w(pose=T(2, 5))))
+    add("warp_bwd_intrinsics: poses (N,5), K cpu", lambda: wk(w(pose=T(2, 5), K=T(2, 3, 3, **CPU))))
+    add("warp_bwd_intrinsics: K of another N", lambda: wk(w(K=T(1, 3, 3))))
+    add("warp_bwd_intrinsics: K ndim", lambda: wk(w(K=T(2, 9))))
+    add("warp_bwd_intrinsics: K of another N, g_warped cpu", lambda: wk(w(K=T(1, 3, 3)), T(2, 3, 8, 8, **CPU)))
+    add("warp_bwd_intrinsics: g_warped of another shape", lambda: wk(w(), T(2, 3, 8, 7)))
+    add("warp_bwd_intrinsics: g_warped ndim", lambda: wk(w(), T(2, 3, 64)))
+    add("warp_bwd_intrinsics: g_warped cpu", lambda: wk(w(), T(2, 3, 8, 8, **CPU)))
+    add("warp_bwd_intrinsics: g_warped float64", lambda: wk(w(depth=T(2, 3, 64)), T(2, 3, 8, 8, **F64)))
+
+    # ops.pose_proj_bwd_intrinsics(pose6, K, g_proj)
+    pk = ops.pose_proj_bwd_intrinsics
+    add("pose_proj_bwd_intrinsics: pose6 ndim", lambda: pk(T(12), T(2, 3, 3), T(2, 4, 4)))
+    add("pose_proj_bwd_intrinsics: pose6 cpu", lambda: pk(T(2, 6, **CPU), T(2, 3, 3), T(2, 4, 4)))
+    add("pose_proj_bwd_intrinsics: K cpu", lambda: pk(T(2, 6), T(2, 3, 3, **CPU), T(2, 4, 4)))
+    add("pose_proj_bwd_intrinsics: K ndim", lambda: pk(T(2, 6), T(2, 9), T(2, 4, 4)))
+    add("pose_proj_bwd_intrinsics: K float64, g_proj cpu", lambda: pk(T(2, 6), T(2, 3, 3, **F64), T(2, 4, 4, **CPU)))
+    add("pose_proj_bwd_intrinsics: g_proj ndim", lambda: pk(T(2, 6), T(2, 3, 3), T(2, 16)))
+    add("pose_proj_bwd_intrinsics: g_proj int32", lambda: pk(T(2, 6), T(2, 3, 3), T(2, 4, 4, **I32)))
+    add("pose_proj_bwd_intrinsics: pose6 (N,5)", lambda: pk(T(2, 5), T(2, 3, 3), T(2, 4, 4)))
+    add("pose_proj_bwd_intrinsics: K of another N", lambda: pk(T(2, 6), T(3, 3, 3), T(2, 4, 4)))
+    add("pose_proj_bwd_intrinsics: K (N,3,4)", lambda: pk(T(2, 6), T(2, 3, 4), T(2, 4, 4)))
+    add("pose_proj_bwd_intrinsics: g_proj (N,3,4)", lambda: pk(T(2, 6), T(2, 3, 3), T(2, 3, 4)))
+    add("pose_proj_bwd_intrinsics: g_proj of another N", lambda: pk(T(2, 6), T(2, 3, 3), T(1, 4, 4)))
     return out
 
 

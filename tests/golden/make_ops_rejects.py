@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Writes ops_rejects.json: what the 18 operator entry points of include/sfmwarp.h (everything outside sfm_loss_* / sfm_step_*)
+"""Writes ops_rejects.json: what the operator entry points of include/sfmwarp.h (everything outside sfm_loss_* / sfm_step_*)
 answer to arguments they reject, and to the accepted calls that return before any launch -- each row a list
-[entry point, arguments, return code, sfm_last_error() text].
+[entry point, arguments, return code, sfm_last_error() text].  ENTRIES are the entry points the table holds; the few whose
+rejections are pinned in a CPU test file of their own are listed in PINNED_ELSEWHERE.
 
 Arguments are written as JSON: an int for an int / size_t, null or FAKE for a pointer, null or a list for an array of pointers
-(0 = a NULL element) or of lengths.  Nothing is launched and no pointer is dereferenced: would_launch() restates the validation of
+(0 = a NULL element) or of lengths, null or a dict of field values for a descriptor (a pointer field: 0 = NULL; an array field: a
+list, the rest of the array zero).  Nothing is launched and no pointer is dereferenced: would_launch() restates the validation of
 each entry point, and a row whose arguments would pass it with work to do is refused before the library sees it.  Before every
 call the last error is set to SENTINEL (a rejected sfm_pyramid_variant), so the text of an accepted call is SENTINEL: accepted
 calls leave the message alone.
@@ -27,7 +29,15 @@ _lib = importlib.import_module("sfm-learner-chainer_amd._lib")
 FAKE = 64                                          # never dereferenced
 P8 = [FAKE] * 8                                    # an array of eight bound pointers
 SENTINEL_VARIANT = 7                               # sfm_pyramid_variant(7) is rejected: its message is the sentinel
-ENTRIES = sorted(n for n in _lib.SYMBOLS if not n.startswith(("sfm_loss_", "sfm_step_")) and n not in ("sfm_abi_version", "sfm_last_error"))
+ALIGNED = 256                                      # a workspace address the library takes; never dereferenced either
+# operator entry points whose rejections are pinned by the CPU tests of their own feature instead of this table
+PINNED_ELSEWHERE = {
+    "sfm_resize_bwd": "tests/test_resize_bwd_cpu.py",
+    "sfm_warp_intrinsics_bwd": "tests/test_intrinsics_grad_cpu.py",
+    "sfm_warp_intrinsics_bwd_workspace_bytes": "tests/test_intrinsics_grad_cpu.py",
+    "sfm_pose_proj_bwd_k": "tests/test_intrinsics_grad_cpu.py",
+}
+SIZES = ("sfm_warp_bwd_workspace_bytes", "sfm_warp_pyramid_bwd_workspace_bytes")      # answer a size_t, not a code
 
 
 def _pyramid(ys, N, images, H, W, S, first):
@@ -54,11 +64,62 @@ def _arrays(a, arrays, numel, n, n_max):
     return all(v >= 0 for v in ln) and all(a[k][i] for k in arrays for i, v in enumerate(ln) if v > 0) and 0 < sum(ln) < 2 ** 40
 
 
+def _pyramid_desc(d, count, tiles, setting, inputs, outputs, per_image=()):
+    """The checks the two descriptor entry points share (check_pyramid_shape of csrc/sfm_common.h, then the setting and the
+    pointers): True if a launch follows.  count: the per-sample count's field; tiles(H, W): the launch units of one image set of a
+    scale; inputs / outputs: the per-scale pointer fields that must be bound; per_image: the per-image ones."""
+    if d is None or not (1 <= d[count] <= 8 and 1 <= d["n_scales"] <= 8 and d["B"] >= 0):
+        return False
+    S, total = d["n_scales"], 0
+    H, W = (d["H"] + [0] * 8)[:S], (d["W"] + [0] * 8)[:S]
+    for h, w in zip(H, W):
+        if h < 3 or w < 3 or 3 * h * w >= 2 ** 31:
+            return False
+        total += d["B"] * tiles(h, w)
+        if total >= 2 ** 31:
+            return False
+    if not setting(d) or d["B"] == 0:
+        return False
+    bound = lambda f, n: all((d[f] + [0] * 8)[:n])
+    return all(bound(f, S) for f in inputs + outputs) and all(bound(f, d[count]) for f in per_image)
+
+
+def warp_pyramid_blocks(H, W):
+    return (H * W + 255) // 256
+
+
+def photo_error_tiles(H, W, n_img, bwd):
+    strip = 60 if bwd else 62
+    return n_img * ((W + strip - 1) // strip) * ((H + 15) // 16)
+
+
+def _warp_pyramid(d, bwd):
+    return _pyramid_desc(d, "n_src", warp_pyramid_blocks, lambda d: d["image_layout"] in (0, 1) and bool(d["intrinsics"]), ["src", "disp"],
+                         ["g_warped", "d_disp"] if bwd else ["warped"], ["pose"] + (["d_pose"] if bwd else []))
+
+
+def warp_pyramid_ws_bytes(d):
+    need = sum(d["B"] * warp_pyramid_blocks(h, w) for h, w in zip(d["H"][:d["n_scales"]], d["W"])) * d["n_src"] * 48
+    return (need + 255) // 256 * 256 if need else 256
+
+
+def _photo_error(d, bwd):
+    return _pyramid_desc(d, "n_img", lambda h, w: photo_error_tiles(h, w, d["n_img"], bwd), lambda d: 0.0 <= d["ssim_rate"] <= 1.0,
+                         ["img", "tgt"], ["g_err", "d_img"] if bwd else ["err"])
+
+
 def would_launch(name, a):
     """True if the library would pass these arguments on to HIP (a kernel launch or a memset): the validation of csrc/sfm_ops.hip,
-    restated.  Such a row has no place in the table: its fake pointers would be used."""
-    if name in ("sfm_pyramid_variant", "sfm_warp_bwd_workspace_bytes"):
+    csrc/sfm_warp_pyramid.hip and csrc/sfm_photo_error.hip, restated.  Such a row has no place in the table: its fake pointers
+    would be used."""
+    if name in ("sfm_pyramid_variant",) + SIZES:
         return False
+    if name == "sfm_warp_pyramid_fwd":
+        return _warp_pyramid(a[0], False)
+    if name == "sfm_warp_pyramid_bwd":
+        return _warp_pyramid(a[0], True) and bool(a[1]) and a[1] % 256 == 0 and a[2] >= warp_pyramid_ws_bytes(a[0])
+    if name in ("sfm_photo_error_fwd", "sfm_photo_error_bwd"):
+        return _photo_error(a[0], name.endswith("bwd"))
     if name in ("sfm_pose_proj_fwd", "sfm_pose_proj_bwd"):
         return all(a[:-2]) and a[-2] > 0
     if name == "sfm_warp_fwd":
@@ -104,13 +165,23 @@ def call(name, args):
             conv.append(v)
         elif v is None:
             conv.append(None)
+        elif isinstance(v, dict):
+            desc = t._type_()
+            for field, value in v.items():
+                if isinstance(value, list):
+                    for k, e in enumerate(value):
+                        getattr(desc, field)[k] = e or None if getattr(desc, field)._type_ is C.c_void_p else e
+                else:
+                    setattr(desc, field, value)
+            keep.append(desc)
+            conv.append(C.byref(desc))
         else:
             arr = (t._type_ * len(v))(*[e or None for e in v] if t._type_ is C.c_void_p else v)
             keep.append(arr)
             conv.append(arr)
     assert _lib.lib.sfm_pyramid_variant(SENTINEL_VARIANT) == _lib.ERR_CONFIG
     rc = getattr(_lib.lib, name)(*conv)
-    assert rc <= 0 or res is C.c_size_t, "%s%r launched: %d %s" % (name, tuple(args), rc, _lib.last_error())
+    assert rc <= 0 or name in SIZES, "%s%r launched: %d %s" % (name, tuple(args), rc, _lib.last_error())
     return int(rc), _lib.last_error()
 
 
@@ -211,7 +282,94 @@ def cases():
         sc(n=32, x=Z33, y=Z33, numel=Z33), sc(n=33, gy=None), sc(n=33, x=None), sc(n=0, gy=None), sc(gy=None, numel=[-1] * 4), sc(numel=[0, 0, 0, -1]),
         sc(numel=[0, 0, 0, -1], x=Z4), sc(numel=[0, 0, 3, 0], x=Z4), sc(numel=[0, 0, 3, 0], y=Z4), sc(numel=[0, 3, -1, 0], y=[F, 0, F, F]),
         sc(numel=[-1, 3, 0, 0], y=[F, 0, F, F]), sc(x=P33, y=P33, numel=[0] * 31 + [-1], n=32), sc(x=P33, y=P33, numel=[0] * 31 + [-1], n=31))
+    return out + _descriptor_cases()
+
+
+def _without(d, field, k=None):
+    """the descriptor `d` with pointer `field` (its element k) NULL"""
+    return dict(d, **{field: 0 if k is None else d[field][:k] + [0] + d[field][k + 1:]})
+
+
+def _descriptor_cases():
+    """sfm_warp_pyramid_* and sfm_photo_error_*: (descriptor, [ws, ws_bytes,] stream).  Both check the counts, B, then per scale
+    the shape and the running launch-unit count, then their setting (image_layout / ssim_rate), return for an empty batch, and only
+    then look at the pointers.  A bound at its edge is shown to pass by the NEXT fault of the same call: a bad setting behind a
+    shape, a NULL pointer behind the setting."""
+    F, out = FAKE, []
+    add = lambda name, *rows: out.extend((name, list(r)) for r in rows)
+    n8 = lambda n: min(max(n, 0), 8)
+    BIG = (32768, 21845)                           # 3*H*W = 2^31 - 32768: the largest frame of this aspect
+
+    def wp(B=1, n_src=2, S=2, H=(8, 4), W=(8, 3), layout=0, p=F, **over):
+        d = dict(B=B, n_src=n_src, n_scales=S, H=list(H), W=list(W), image_layout=layout, src=[p] * n8(S), disp=[p] * n8(S), intrinsics=p,
+                 pose=[p] * n8(n_src), warped=[p] * n8(S), valid=[0] * n8(S), g_warped=[p] * n8(S), d_disp=[p] * n8(S), d_pose=[p] * n8(n_src))
+        return dict(d, **over)
+
+    def shapes(mk, bad):
+        """the rows both descriptors share; `bad`: a setting past its bound (the check behind the shapes)"""
+        one = 2 ** 31 // 3
+        return [None, mk(**{mk.count: 0}), mk(**{mk.count: 9}), mk(**{mk.count: -1}), mk(**{mk.count: 1, **bad}), mk(**{mk.count: 8, **bad}),
+                mk(S=0), mk(S=9), mk(S=-1), mk(S=1, **bad), mk(S=8, H=[8] * 8, W=[8] * 8, **bad), mk(**{mk.count: 0, "S": 0}),
+                mk(**{mk.count: 9, "B": -1}), mk(S=9, B=-1), mk(B=-1), mk(B=-1, H=(2, 4)), mk(B=-1, p=0),
+                mk(H=(2, 4)), mk(W=(2, 4)), mk(H=(8, 2)), mk(W=(8, 2)), mk(H=(3, 3), W=(3, 3), **bad), mk(H=(2, 2)), mk(H=(8, 2), **bad),
+                mk(H=(0, 4)), mk(W=(8, -1)), mk(S=1, H=(8, 2), **bad),
+                mk(S=1, H=BIG[:1], W=(BIG[1] + 1,)), mk(S=1, H=BIG[:1], W=BIG[1:], **bad), mk(H=(8, BIG[0]), W=(8, BIG[1] + 1)),
+                mk(H=(2, BIG[0]), W=(8, BIG[1] + 1)), mk(S=1, H=(one + 1,), W=(1,)), mk(S=1, H=(3,), W=(one + 1,)), mk(S=1, H=(3,), W=(one // 3 + 1,)),
+                mk(S=1, H=(65536,), W=(65536,)), mk(B=0, S=1, H=BIG[:1], W=(BIG[1] + 1,)), mk(B=0, p=0), mk(B=0), mk(B=0, **bad), mk(B=0, p=0, **bad),
+                mk(B=0, S=8, H=[3] * 8, W=[3] * 8, p=0, **{mk.count: 8})]
+    wp.count = "n_src"
+
+    def overflow(mk, per, **kw):
+        """the running count of launch units at 2^31 - 1 and one past it: in one scale, and summed over two; `per`: one image set"""
+        edge = (2 ** 31 - 1) // per
+        half = (2 ** 31 - 1) // (2 * per)
+        big2 = dict(S=2, H=BIG[:1] * 2, W=BIG[1:] * 2)
+        return [mk(B=edge, S=1, H=BIG[:1], W=BIG[1:], p=0, **kw), mk(B=edge + 1, S=1, H=BIG[:1], W=BIG[1:], **kw), mk(B=half, p=0, **big2, **kw),
+                mk(B=half + 1, **big2, **kw), mk(B=edge + 1, S=2, H=(BIG[0], 2), W=(BIG[1], 8), **kw), mk(B=2 ** 31 - 1, **kw)]
+
+    # sfm_warp_pyramid_fwd: desc, stream
+    nulls = lambda d, fields: [_without(d, "intrinsics")] + [_without(d, f, k) for f in fields for k in range(2)]
+    rows = shapes(wp, dict(layout=2)) + overflow(wp, warp_pyramid_blocks(*BIG)) + nulls(wp(), ("src", "disp", "warped", "pose")) + [
+        wp(layout=-1), wp(layout=2, p=0), wp(layout=1, intrinsics=0), wp(layout=1, p=0), wp(intrinsics=0, src=[0, 0]), wp(src=[F, 0], disp=[0, F]),
+        wp(src=[0, F], disp=[0, F]), wp(disp=[0, F], warped=[0, F]), wp(warped=[F, 0], pose=[0, F]), wp(pose=[0, 0]), wp(S=1, n_src=1, warped=[0], g_warped=[0]),
+        wp(S=8, H=[8] * 8, W=[8] * 8, warped=[F] * 7 + [0]), wp(n_src=8, pose=[F] * 7 + [0])]
+    add("sfm_warp_pyramid_fwd", *[[d, None] for d in rows])
+
+    # sfm_warp_pyramid_bwd_workspace_bytes: desc -> bytes, 0 for a descriptor sfm_warp_pyramid_bwd refuses (the backward's pointers)
+    both = shapes(wp, dict(layout=2)) + overflow(wp, warp_pyramid_blocks(*BIG))
+    bwd_nulls = nulls(wp(), ("src", "disp", "g_warped", "d_disp", "pose", "d_pose")) + [
+        wp(layout=2, p=0), wp(g_warped=[F, 0], d_disp=[0, F]), wp(g_warped=[0, F], d_disp=[0, F]), wp(d_disp=[F, 0], pose=[0, F]),
+        wp(pose=[0, F], d_pose=[0, F]), wp(pose=[F, 0], d_pose=[0, F]), wp(n_src=8, d_pose=[F] * 7 + [0])]
+    sizes = [wp(), wp(warped=[0, 0]), wp(B=2), wp(B=3, n_src=3, S=3, H=(16, 8, 4), W=(24, 12, 6)), wp(S=1, H=(3,), W=(3,), n_src=1), wp(S=1, H=(16,), W=(16,)),
+             wp(S=1, H=(16,), W=(17,), n_src=8), wp(B=4, S=1, H=(128,), W=(416,), layout=1)]
+    add("sfm_warp_pyramid_bwd_workspace_bytes", *[[d] for d in both + bwd_nulls + sizes])
+
+    # sfm_warp_pyramid_bwd: desc, ws, ws_bytes, stream.  The workspace is the last check: its size, then its alignment
+    good = wp()
+    need = warp_pyramid_ws_bytes(good)
+    add("sfm_warp_pyramid_bwd", *[[d, ALIGNED, 1 << 40, None] for d in both + bwd_nulls],
+        [good, None, need, None], [good, None, 0, None], [good, ALIGNED, need - 1, None], [good, ALIGNED, 0, None], [good, F, need, None],
+        [good, F, need - 1, None], [good, ALIGNED + 4, 1 << 40, None], [wp(warped=[0, 0]), None, need, None], [wp(d_pose=[0, F]), None, 0, None],
+        [wp(layout=2), None, 0, None], [wp(B=0, p=0), None, 0, None], [wp(B=0), F, 0, None], [None, None, 0, None])
+
+    # sfm_photo_error_fwd / _bwd: desc, stream
+    def pe(B=1, n_img=2, S=2, H=(8, 4), W=(8, 3), ssim_rate=0.15, p=F, **over):
+        d = dict(B=B, n_img=n_img, n_scales=S, H=list(H), W=list(W), ssim_rate=ssim_rate, img=[p] * n8(S), tgt=[p] * n8(S), err=[p] * n8(S),
+                 g_err=[p] * n8(S), d_img=[p] * n8(S))
+        return dict(d, **over)
+    pe.count = "n_img"
+    for name, bwd, outs in (("sfm_photo_error_fwd", False, ("err",)), ("sfm_photo_error_bwd", True, ("g_err", "d_img"))):
+        rows = shapes(pe, dict(ssim_rate=1.5)) + overflow(pe, photo_error_tiles(*BIG, 1, bwd), n_img=1) + overflow(pe, photo_error_tiles(*BIG, 8, bwd), n_img=8) \
+            + nulls(pe(), ("img", "tgt") + outs)[1:] + [
+            pe(ssim_rate=-0.5), pe(ssim_rate=-1e-6), pe(ssim_rate=1.0 + 2.0 ** -23), pe(ssim_rate=0.0, p=0), pe(ssim_rate=-0.0, p=0), pe(ssim_rate=1.0, p=0),
+            pe(ssim_rate=1.0, img=[F, 0]), pe(ssim_rate=2.0, p=0), pe(img=[F, 0], tgt=[0, F]), pe(img=[0, F], tgt=[0, F]), pe(tgt=[0, F], **{outs[0]: [0, F]}),
+            pe(**{outs[0]: [F, 0], outs[-1]: [0, F]}), pe(S=8, H=[8] * 8, W=[8] * 8, **{outs[-1]: [F] * 7 + [0]}),
+            pe(S=1, H=(3,), W=(3,), n_img=1, **{outs[0]: [0], ("err" if bwd else "g_err"): [0]})]
+        add(name, *[[d, None] for d in rows])
     return out
+
+
+ENTRIES = sorted({name for name, _ in cases()})
 
 
 def table():

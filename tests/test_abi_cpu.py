@@ -2,30 +2,49 @@
 declares; argument validation (which happens before any HIP call) follows the error convention."""
 import ctypes as C
 import importlib
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
+
 _lib = importlib.import_module("sfm-learner-chainer_amd._lib")
-
-
-def _declared_symbols():
-    text = open(os.path.join(ROOT, "include", "sfmwarp.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sfm_[a-z0-9_]+)\s*\(", text)))
+DESCRIPTORS = {"SfmLossDesc": _lib.SfmLossDesc, "SfmWarpPyramidDesc": _lib.SfmWarpPyramidDesc, "SfmPhotoErrorDesc": _lib.SfmPhotoErrorDesc}
 
 
 def test_header_and_binding_declare_the_same_symbols():
-    assert _declared_symbols() == sorted(_lib.SYMBOLS)
+    assert abi_header.declared() == sorted(_lib.SYMBOLS) == sorted(abi_header.prototypes())
 
 
 def test_library_exports_every_declared_symbol():
     raw = C.CDLL(_lib.LIB_PATH)
-    for name in _declared_symbols():
+    for name in abi_header.declared():
         assert hasattr(raw, name), name
     assert raw.sfm_abi_version() == _lib.SFM_ABI_VERSION
+
+
+def test_the_abi_version_and_every_descriptor_layout_match_the_header():
+    """One header, one version: an entry point added to it leaves the older declarations as they were exactly when the version and
+    the three descriptors still are what the binding says (the descriptor BYTES are pinned by tests/golden/host_plans.npz)."""
+    assert re.findall(r"#define SFM_ABI_VERSION (\d+)", abi_header.TEXT) == ["6"] and _lib.SFM_ABI_VERSION == 6
+    assert sorted(re.findall(r"typedef struct (\w+)", abi_header.TEXT)) == sorted(DESCRIPTORS)
+    for name, struct in DESCRIPTORS.items():
+        abi_header.assert_layout(struct, name)
+
+
+def _is_pointer(t):
+    return t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer)
+
+
+def test_every_binding_has_the_parameters_of_its_prototype():
+    """per symbol: as many argtypes as the prototype has parameters, and a pointer type wherever the header has a pointer"""
+    for name, (res, args) in _lib.SYMBOLS.items():
+        params = abi_header.parameters(name)
+        assert len(args) == len(params), (name, params)
+        for k, (t, param) in enumerate(zip(args, params)):
+            assert _is_pointer(t) == ("*" in param), (name, k, param, t)
+        fn = getattr(_lib.lib, name)
+        assert fn.argtypes == args and fn.restype == res, name
 
 
 def test_descriptor_layout_matches_the_header():

@@ -1,5 +1,6 @@
 """No GPU needed: the table of entry points tests/test_buffer_contracts_gpu.py covers, held against the prototypes of
 include/sfmwarp.h, and the arena helper itself (util.Arena) on a host tensor."""
+import ast
 import os
 import re
 
@@ -7,37 +8,39 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import test_buffer_contracts_gpu as T
 from util import SENTINEL, Arena
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def prototypes():
-    """name -> parameter list (text) of every function include/sfmwarp.h declares"""
-    text = open(os.path.join(ROOT, "include", "sfmwarp.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sfm_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
 
 
 def takes_a_device_pointer(params):
-    """a float / void pointer or an SfmLossDesc (which binds device pointers); `const char *` and friends do not count"""
-    return bool(re.search(r"\b(float|void)\b[^,]*\*", params)) or "SfmLossDesc" in params
+    """a float / void pointer or a descriptor (which binds device pointers); `const char *` and friends do not count"""
+    return bool(re.search(r"\b(float|void)\b[^,]*\*", params)) or bool(re.search(r"\bSfm(Loss|WarpPyramid|PhotoError)Desc\b", params))
+
+
+def defined_tests(module="test_buffer_contracts_gpu.py"):
+    """the ids ("name", or "file.py::name" for another module) of the test functions a GPU test module defines, read from its source:
+    importing some of them touches the device"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), module)) as f:
+        tree = ast.parse(f.read())
+    prefix = "" if module == "test_buffer_contracts_gpu.py" else module + "::"
+    return {prefix + node.name for node in tree.body if isinstance(node, ast.FunctionDef) and node.name.startswith("test_")}
 
 
 def test_every_entry_point_with_a_device_pointer_is_covered():
-    protos = prototypes()
+    protos = abi_header.prototypes()
     assert len(protos) >= 30 and "sfm_loss_fwd_bwd" in protos and "sfm_scale_arrays" in protos, sorted(protos)
     need = {n for n, p in protos.items() if takes_a_device_pointer(p)}
-    host_only = {"sfm_loss_workspace_bytes", "sfm_loss_plan_info"}      # read the descriptor's integers on the host, launch nothing
+    # read the descriptor's integers on the host, launch nothing
+    host_only = {"sfm_loss_workspace_bytes", "sfm_loss_plan_info", "sfm_warp_pyramid_bwd_workspace_bytes"}
     assert host_only <= need
     need -= host_only
     assert T.EXEMPT <= need, "an exempt name is not (or no longer) an entry point with a pointer argument"
     assert set(T.COVERED) == need - T.EXEMPT, (sorted(need - T.EXEMPT - set(T.COVERED)), sorted(set(T.COVERED) - need))
     assert not (set(T.COVERED) & T.EXEMPT)
     for name, test in T.COVERED.items():
-        assert callable(getattr(T, test, None)), (name, test)
+        assert test in defined_tests(*test.split("::")[:-1]), (name, test)
     # the operator cases are named test ids: every operator entry point of the table appears in them
     short = {i.split("-")[0] for i in T.OP_IDS}
     for name in T.COVERED:
@@ -60,6 +63,14 @@ def test_fused_case_list_covers_what_it_must():
     assert len(oracle) >= 6 and {c.mode for c in oracle} == set(T.MODES)
     assert {c.layout for c in oracle} == {"planar", "hwc"} and {c.proj for c in oracle} == {"fast", "reference_order"}
     assert any(c.step for c in cases)
+    # sfm_loss_proj_bwd: the library's own kernel choice on the three small shapes, every mode, both layouts and projections, with and
+    # without d_src, and behind sfm_step_fwd_bwd too
+    proj = T.PROJ_CASES
+    assert len(proj) == 12 and {c.shape for c in proj} == {(1, 3, 3, 1, 1), (1, 5, 61, 2, 1), (2, 37, 71, 3, 3)} and {c.variant for c in proj} == {0}
+    assert {c.mode for c in proj} == set(T.MODES) and {c.layout for c in proj} == {"planar", "hwc"}
+    assert {c.proj for c in proj} == {"fast", "reference_order"} and {c.dsrc for c in proj} == {"no", "all", "sub"}
+    assert {e for c in proj for e in T.proj_entries_of(c)} == {("bwd", 0), ("fwd_bwd", 1), ("step_fwd_bwd", 1)}
+    assert T.COVERED["sfm_loss_proj_bwd"] == "test_fused_proj_bwd_after_every_gradient_entry"
 
 
 def test_arena_places_guards_and_names_the_damage():

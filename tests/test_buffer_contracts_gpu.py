@@ -69,8 +69,9 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 FINITE_FILL = 1e30
 
-# Entry points of include/sfmwarp.h that take a device pointer -> the test functions of this module that place their buffers in an
-# arena (tests/test_buffer_contracts_cpu.py holds this table against the header's prototypes and against this module's names).
+# Entry points of include/sfmwarp.h that take a device pointer -> the test function that places their buffers in an arena: one of
+# this module, or "file.py::test_name" of another GPU test module (tests/test_buffer_contracts_cpu.py holds this table against the
+# header's prototypes and against the names the modules define).
 COVERED = {
     "sfm_loss_fwd": "test_fused_guards_and_inputs", "sfm_loss_bwd": "test_fused_guards_and_inputs",
     "sfm_loss_fwd_bwd": "test_fused_guards_and_inputs", "sfm_step_fwd": "test_fused_guards_and_inputs",
@@ -83,6 +84,11 @@ COVERED = {
     "sfm_pyramid_hwc_fwd": "test_op_guards_and_inputs", "sfm_pyramid_pair_hwc_fwd": "test_op_guards_and_inputs",
     "sfm_disp_act_fwd": "test_op_guards_and_inputs", "sfm_disp_act_bwd": "test_op_guards_and_inputs",
     "sfm_augment_fwd": "test_op_guards_and_inputs", "sfm_scale_arrays": "test_scale_arrays_in_an_arena",
+    "sfm_pose_proj_bwd_k": "test_op_guards_and_inputs", "sfm_warp_intrinsics_bwd": "test_op_guards_and_inputs",
+    "sfm_loss_proj_bwd": "test_fused_proj_bwd_after_every_gradient_entry",
+    "sfm_resize_bwd": "test_resize_bwd_gpu.py::test_buffer_contract",
+    "sfm_warp_pyramid_fwd": "test_warp_pyramid_gpu.py::test_buffer_contract", "sfm_warp_pyramid_bwd": "test_warp_pyramid_gpu.py::test_buffer_contract",
+    "sfm_photo_error_fwd": "test_photo_error_gpu.py::test_buffer_contract", "sfm_photo_error_bwd": "test_photo_error_gpu.py::test_buffer_contract",
 }
 # measurement and debug hooks: they take a pointer but no tensor of the contract (events; a trace buffer sized by the caller)
 EXEMPT = {"sfm_loss_profile_events", "sfm_loss_debug_trace"}
@@ -369,9 +375,10 @@ def reference(ops, synth, dev, c, entry):
 class Placed:
     """All buffers of one fused-loss call in one arena, a FusedLoss bound to them (bind(buffers=...))."""
 
-    def __init__(self, ops, synth, dev, c, entry, scheme="aligned", ws_room=0):
+    def __init__(self, ops, synth, dev, c, entry, scheme="aligned", ws_room=0, extra=None):
         """ws_room: bytes the workspace REGION has beyond the queried size (for another descriptor's call on the same memory); the
-        call under test is always handed exactly the queried bytes."""
+        call under test is always handed exactly the queried bytes.  extra: name -> shape of further buffers of the arena that the
+        entry point itself does not know (the outputs of sfm_loss_proj_bwd)."""
         self.c, self.entry, self.ops = c, entry, ops
         self.want, self.ws_bytes = reference(ops, synth, dev, c, entry)
         d = self.d = case_inputs(synth, c)
@@ -383,8 +390,10 @@ class Placed:
             by_scale.setdefault(n[-1] if n[-1].isdigit() else "x", []).append(n)
         for group in by_scale.values():
             names += group
-        res = residues_for(names, scheme, outputs=set(self.outs))
-        specs = [(n, (self.ins[n].shape if n in self.ins else self.outs[n]), res[n]) for n in names]
+        extra = extra or {}
+        names += list(extra)
+        res = residues_for(names, scheme, outputs=set(self.outs) | set(extra))
+        specs = [(n, (self.ins[n].shape if n in self.ins else extra[n] if n in extra else self.outs[n]), res[n]) for n in names]
         self.ws_region = max(self.ws_bytes, -(-int(ws_room) // 256) * 256)
         specs.append(("ws", self.ws_region, "ws"))
         self.arena = ar = Arena(dev, specs, row_floats=3 * c.shape[3] * c.shape[2])
@@ -516,6 +525,90 @@ def test_fused_old_output_content_is_not_read(ops, synth, dev, c):
             for n in got:
                 if not n.startswith("d_src"):
                     assert_bits(got[n], p.want[n], "%s d_src pre-filled: %s" % (p.what, n))
+
+
+# sfm_loss_proj_bwd: the library's own choice of kernel (after hooks 4 / 5 the header leaves its result unspecified), small shapes
+PROJ_CASES = [c for c in FUSED_CASES if c.variant == 0 and c.shape in (A, BS, F3)]
+PROJ_OUTS = ("d_proj", "d_intrinsics")
+
+
+def proj_entries_of(c):
+    """(gradient entry point, the `loss` argument that says which one left the sums)"""
+    return (("bwd", 0), ("fwd_bwd", 1)) + ((("step_fwd_bwd", 1),) if c.step else ())
+
+
+def _proj_bwd(ops, fl, loss, d_proj, d_intrinsics):
+    import torch
+    ops._launch(fl.device, ops.lib.sfm_loss_proj_bwd, fl._desc_ref, loss, fl._ws_arg, fl._ws_bytes,
+                C.c_void_p(d_proj) if d_proj else None, C.c_void_p(d_intrinsics) if d_intrinsics else None)
+    torch.cuda.synchronize()
+
+
+def proj_reference(ops, synth, dev, c, entry, loss):
+    """the same sequence -- the gradient entry point, then sfm_loss_proj_bwd -- on conventional allocations.  -> name -> host array"""
+    import torch
+    key = (fcase_id(c), entry, "proj")
+    if key not in _ref_cache:
+        d = case_inputs(synth, c)
+        step = entry.startswith("step")
+        ins, outs = fused_buffers(d, c, step)
+        t = {k: to_dev(v, dev) for k, v in ins.items()}
+        t.update({k: torch.empty(shape, dtype=torch.float32, device=dev) for k, shape in outs.items() if k.startswith(("tgt", "src"))})
+        B, _, _, n_src, S = c.shape
+        fl = _bind_from(ops, c, t.__getitem__, S, n_src, "mask0" in ins)
+        fl.ws.zero_()
+        _launch(ops, fl, c, entry, (t.get("tgt_full"), t.get("src_full")))
+        out = dict(d_proj=torch.empty((B, S, n_src, 3, 4), device=dev), d_intrinsics=torch.empty((B, S, 3, 3), device=dev))
+        _proj_bwd(ops, fl, loss, out["d_proj"].data_ptr(), out["d_intrinsics"].data_ptr())
+        _ref_cache[key] = {k: to_np(v).copy() for k, v in out.items()}
+    return _ref_cache[key]
+
+
+@pytest.mark.parametrize("c", PROJ_CASES, ids=fcase_id)
+def test_fused_proj_bwd_after_every_gradient_entry(ops, synth, dev, c):
+    """sfm_loss_proj_bwd behind sfm_loss_bwd (loss = 0), sfm_loss_fwd_bwd and sfm_step_fwd_bwd (loss = 1), d_proj and d_intrinsics two
+    more buffers of the arena.  The guards stay intact; every input and the WHOLE workspace keep their bits ("reads `ws`, never writes
+    it"); both outputs are written completely and hold the bits of the same sequence on conventional allocations, whether they held
+    1e30 or the sentinel before and at every residue scheme; with one of them NULL the other has the same bits and the NULL one's
+    buffer keeps every sentinel."""
+    import torch
+    B, _, _, n_src, S = c.shape
+    extra = collections.OrderedDict(d_proj=(B, S, n_src, 3, 4), d_intrinsics=(B, S, 3, 3))
+    for entry, loss in proj_entries_of(c):
+        want = proj_reference(ops, synth, dev, c, entry, loss)
+        for scheme in ("aligned",) + SCHEMES:
+            p = Placed(ops, synth, dev, c, entry, scheme=scheme, extra=extra)
+            ar = p.arena
+            p.verify(p.run())                                    # the gradient call itself, as in check 1
+            ws_before = ar.raw("ws").clone()
+            outs_before = {n: ar.raw(n).clone() for n in p.outs}
+            ptr = {n: ar.ptr(n) for n in PROJ_OUTS}
+
+            def call(what, fill, **null):
+                """one call with both outputs pre-filled by `fill`; null: the outputs passed as NULL"""
+                for n in PROJ_OUTS:
+                    fill(n)
+                _proj_bwd(ops, p.fl, loss, *[None if n in null else ptr[n] for n in PROJ_OUTS])
+                what = "%s: sfm_loss_proj_bwd %s" % (p.what, what)
+                ar.check(what)
+                for n in p.ins:
+                    ar.unchanged(n)
+                assert torch.equal(ar.raw("ws"), ws_before), "%s wrote the workspace" % what
+                for n in p.outs:
+                    assert torch.equal(ar.raw(n), outs_before[n]), "%s wrote %s" % (what, n)
+                for n in PROJ_OUTS:
+                    if n not in null:
+                        assert_bits(to_np(ar.view(n)), want[n], "%s: %s" % (what, n))
+                return what
+
+            what = call("outputs pre-filled with the sentinel", ar.fill_bits)
+            for n in PROJ_OUTS:
+                assert ar.sentinels_left(n) == 0, "%s: %d elements of %s were never written" % (what, ar.sentinels_left(n), n)
+            if scheme == "aligned":
+                call("outputs pre-filled with 1e30", lambda n: ar.fill(n, FINITE_FILL))
+                for n in PROJ_OUTS:
+                    what = call("with %s = NULL" % n, ar.fill_bits, **{n: True})
+                    assert ar.sentinels_left(n) == ar.nbytes(n) // 4, "%s: yet its buffer was written" % what
 
 
 def _other_descriptor(ops, synth, dev, c):
@@ -694,6 +787,8 @@ def _op_cases(ops, synth):
         ins = dict(pose=pose, K=K.astype(F32), g_proj=rnd(N, 4, 4))
         cases.append(OpCase("pose_proj_bwd-N%d" % N, "sfm_pose_proj_bwd", ins, dict(d_pose=((N, 6), "over")),
                             lambda p, w, nb, st, N=N: L.sfm_pose_proj_bwd(p("pose"), p("K"), p("g_proj"), p("d_pose"), N, st)))
+        cases.append(OpCase("pose_proj_bwd_k-N%d" % N, "sfm_pose_proj_bwd_k", ins, dict(d_K=((N, 3, 3), "over")),
+                            lambda p, w, nb, st, N=N: L.sfm_pose_proj_bwd_k(p("pose"), p("K"), p("g_proj"), p("d_K"), N, st)))
 
     # ---- projective_inverse_warp
     for (N, Cc, H, W, drows, with_src) in ((1, 3, 3, 3, 1, True), (2, 3, 8, 61, 3, False), (2, 2, 33, 65, 1, True), (1, 3, 16, 64, 3, True)):
@@ -714,6 +809,10 @@ def _op_cases(ops, synth):
                                 p("src"), p("depth"), r, p("pose"), p("K"), p("g_warped"), p("d_depth"), p("d_pose"), p("d_src") if ws_ else None,
                                 w, nb, *a, st),
                             ws=int(L.sfm_warp_bwd_workspace_bytes(N, H, W)), row=W))
+        cases.append(OpCase("warp_intrinsics_bwd-" + tag, "sfm_warp_intrinsics_bwd", ins, dict(d_K=((N, 3, 3), "over")),
+                            lambda p, w, nb, st, a=(N, Cc, H, W), r=drows: L.sfm_warp_intrinsics_bwd(
+                                p("src"), p("depth"), r, p("pose"), p("K"), p("g_warped"), p("d_K"), w, nb, *a, st),
+                            ws=int(L.sfm_warp_intrinsics_bwd_workspace_bytes(N, H, W)), row=W))
 
     # ---- the two samplers
     for (family, N, Cc, H, W, oH, oW, with_gx) in (("shift", 1, 1, 4, 66, 1, 65, True), ("smooth", 2, 3, 9, 61, 8, 65, True),
@@ -822,9 +921,12 @@ def op_cases(ops, synth):
 
 
 # the ids, spelled out so that every case is a named test (the list is checked against what _op_cases builds)
-OP_IDS = """pose_proj_fwd-N1 pose_proj_bwd-N1 pose_proj_fwd-N64 pose_proj_bwd-N64 pose_proj_fwd-N65 pose_proj_bwd-N65
-warp_fwd-N1-C3-3x3-rows1 warp_bwd-N1-C3-3x3-rows1-d_src warp_fwd-N2-C3-8x61-rows3 warp_bwd-N2-C3-8x61-rows3-null_d_src
-warp_fwd-N2-C2-33x65-rows1 warp_bwd-N2-C2-33x65-rows1-d_src warp_fwd-N1-C3-16x64-rows3 warp_bwd-N1-C3-16x64-rows3-d_src
+OP_IDS = """pose_proj_fwd-N1 pose_proj_bwd-N1 pose_proj_bwd_k-N1 pose_proj_fwd-N64 pose_proj_bwd-N64 pose_proj_bwd_k-N64
+pose_proj_fwd-N65 pose_proj_bwd-N65 pose_proj_bwd_k-N65
+warp_fwd-N1-C3-3x3-rows1 warp_bwd-N1-C3-3x3-rows1-d_src warp_intrinsics_bwd-N1-C3-3x3-rows1
+warp_fwd-N2-C3-8x61-rows3 warp_bwd-N2-C3-8x61-rows3-null_d_src warp_intrinsics_bwd-N2-C3-8x61-rows3
+warp_fwd-N2-C2-33x65-rows1 warp_bwd-N2-C2-33x65-rows1-d_src warp_intrinsics_bwd-N2-C2-33x65-rows1
+warp_fwd-N1-C3-16x64-rows3 warp_bwd-N1-C3-16x64-rows3-d_src warp_intrinsics_bwd-N1-C3-16x64-rows3
 sampler_fwd-shift-N1-C1-4x66-to-1x65 sampler_bwd-shift-N1-C1-4x66-to-1x65-gx sampler_interp_fwd-shift-N1-C1-4x66-to-1x65
 sampler_interp_bwd-shift-N1-C1-4x66-to-1x65-gx sampler_fwd-smooth-N2-C3-9x61-to-8x65 sampler_bwd-smooth-N2-C3-9x61-to-8x65-gx
 sampler_interp_fwd-smooth-N2-C3-9x61-to-8x65 sampler_interp_bwd-smooth-N2-C3-9x61-to-8x65-gx sampler_fwd-zoom2-N2-C5-32x64-to-33x64
@@ -845,8 +947,10 @@ augment-C3-F5-17x23 augment-C4-F1-32x104 augment-C3-F1-9x7""".split()
 
 def test_op_case_list_is_complete(ops, synth):
     assert list(op_cases(ops, synth)) == OP_IDS
-    assert {c.entry for c in op_cases(ops, synth).values()} | {"sfm_scale_arrays"} | {k for k in COVERED if k.startswith(("sfm_loss", "sfm_step"))} \
-        == set(COVERED)
+    assert len(OP_IDS) == 72 and len(set(OP_IDS)) == 72
+    here = {k for k, test in COVERED.items() if "::" not in test}
+    assert {c.entry for c in op_cases(ops, synth).values()} | {"sfm_scale_arrays"} | {k for k in here if k.startswith(("sfm_loss", "sfm_step"))} == here
+    assert {k for k, test in COVERED.items() if test == "test_op_guards_and_inputs"} == {c.entry for c in op_cases(ops, synth).values()}
 
 
 def op_reference(ops, dev, oc):
@@ -945,10 +1049,11 @@ def test_op_old_output_content_is_not_read(ops, synth, dev, ident):
         p.verify(p.run(acc_prefill=pre), " accumulated outputs pre-filled", acc_prefill=pre)
 
 
-@pytest.mark.parametrize("ident", [i for i in OP_IDS if i.startswith("warp_bwd")])
+@pytest.mark.parametrize("ident", [i for i in OP_IDS if i.startswith(("warp_bwd-", "warp_intrinsics_bwd-"))])
 def test_op_stale_scratch(ops, synth, dev, ident):
-    """Check 3 for the one operator with a workspace (sfm_warp_bwd: the per-block pose partials): exactly the queried bytes, holding
-    zeros, the NaN sentinel, 0xFF bytes, or the partials of a call on other inputs -- the same bits; one byte less is rejected."""
+    """Check 3 for the two operators with a workspace (sfm_warp_bwd: the per-block pose partials; sfm_warp_intrinsics_bwd: the
+    per-block sums of gPm and G): exactly the queried bytes, holding zeros, the NaN sentinel, 0xFF bytes, or the partials of a call
+    on other inputs -- the same bits; one byte less is rejected."""
     oc = op_cases(ops, synth)[ident]
     p = PlacedOp(ops, dev, oc)
     for kind, word in (("zeros", 0), ("sentinel", SENTINEL), ("0xFF", 0xFFFFFFFF)):
@@ -970,7 +1075,7 @@ def test_op_stale_scratch(ops, synth, dev, ident):
     torch.cuda.synchronize()
     p.arena.check(p.what)
     for n in list(oc.outs) + ["ws"]:
-        assert p.arena.sentinels_left(n) == p.arena.nbytes(n) // 4, "a rejected sfm_warp_bwd wrote %s" % n
+        assert p.arena.sentinels_left(n) == p.arena.nbytes(n) // 4, "a rejected %s wrote %s" % (oc.entry, n)
 
 
 @_op_ids

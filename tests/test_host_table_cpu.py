@@ -53,7 +53,8 @@ def test_the_refusals_are_the_fixture(rejects):
     heads = {r[0].split(":")[0] for r in rejects}
     assert {"resize", "pose_proj_fwd", "pose_proj_bwd", "warp_fwd", "warp_bwd", "sampler_fwd", "sampler_bwd", "interp_fwd",
             "interp_bwd", "pyramid", "pyramid_hwc", "pyramid_pair_hwc", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "bind", "loss",
-            "scale_arrays_into", "disp_activation", "augment_images"} <= heads
+            "scale_arrays_into", "disp_activation", "augment_images", "warp_pyramid", "photometric_error", "warp_pyramid_fwd",
+            "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "resize_bwd", "warp_bwd_intrinsics", "pose_proj_bwd_intrinsics"} <= heads
 
 
 def test_every_refusal_has_the_pinned_class_and_text(rejects):

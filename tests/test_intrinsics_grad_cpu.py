@@ -1,5 +1,5 @@
 """The gradient with respect to the camera intrinsics without a GPU: the derivation, the reference floors that hold the margins of
-tests/test_intrinsics_grad_gpu.py, the reject paths of the three entry points (include/sfmwarp_intrinsics.h) and
+tests/test_intrinsics_grad_gpu.py, the reject paths of the three entry points (include/sfmwarp.h) and
 torch_api.multi_scale_intrinsics.
 
 The derivation.  Per (sample, scale) and source i, with Pm = K [R|t] (models/transform.py:86-88), ray = K^-1 pix (:105), one depth per
@@ -9,16 +9,15 @@ pixel (models/base_model.py:82-84) and gPm = dL/dPm:
 restatement of the reference in tests/test_oracle_vs_torch_cpu.py, is the judge."""
 import ctypes as C
 import importlib
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import intrinsics_grad as IG
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _lib = importlib.import_module("sfm-learner-chainer_amd._lib")
 ops = importlib.import_module("sfm-learner-chainer_amd.ops")
 ta = importlib.import_module("sfm-learner-chainer_amd.torch_api")
@@ -31,16 +30,15 @@ IDS = ["%s-%s" % ("x".join(map(str, s)), k) for s, k in CASES]
 # ------------------------------------------------------------------------------------------------------------------------
 # header and binding
 # ------------------------------------------------------------------------------------------------------------------------
+ENTRY_POINTS = ["sfm_loss_proj_bwd", "sfm_pose_proj_bwd_k", "sfm_warp_intrinsics_bwd", "sfm_warp_intrinsics_bwd_workspace_bytes"]
+
+
 def test_header_binding_and_library_declare_the_same_symbols():
-    text = open(os.path.join(ROOT, "include", "sfmwarp_intrinsics.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sfm_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(_lib.INTRINSICS_SYMBOLS) == ["sfm_loss_proj_bwd", "sfm_pose_proj_bwd_k", "sfm_warp_intrinsics_bwd",
-                                                          "sfm_warp_intrinsics_bwd_workspace_bytes"]
-    assert not set(_lib.INTRINSICS_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.EXT_SYMBOLS))
-    assert '#include "sfmwarp.h"' in text and "SFM_ABI_VERSION" not in text and "typedef" not in text
-    for name, (_, args) in _lib.INTRINSICS_SYMBOLS.items():
-        assert getattr(L, name).argtypes == args
+    pick = lambda names: sorted(n for n in names if re.search(r"intrinsics|proj_bwd_k|loss_proj", n))
+    assert pick(abi_header.declared()) == pick(_lib.SYMBOLS) == ENTRY_POINTS
+    for name in ENTRY_POINTS:
+        res, args = _lib.SYMBOLS[name]
+        assert getattr(L, name).argtypes == args and getattr(L, name).restype == res, name
 
 
 # ------------------------------------------------------------------------------------------------------------------------

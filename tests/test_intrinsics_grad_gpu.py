@@ -1,5 +1,5 @@
 """The gradient with respect to the camera intrinsics on the GPU: sfm_loss_proj_bwd behind every kind of gradient launch of the fused
-loss, sfm_warp_intrinsics_bwd and sfm_pose_proj_bwd_k (include/sfmwarp_intrinsics.h).
+loss, sfm_warp_intrinsics_bwd and sfm_pose_proj_bwd_k (include/sfmwarp.h).
 
   1. self-consistency: d_intrinsics against the closed form (tests/intrinsics_grad.py, NumPy fp64) evaluated on the library's own
      d_proj, 1e-5 per entry -- the kernel works in fp64 and the test's input is rounded once (CPU floor 9.2e-7,

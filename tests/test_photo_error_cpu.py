@@ -1,82 +1,43 @@
-"""The photometric error maps (include/sfmwarp_photo_error.h) without a GPU: header, binding and library declare the same two entry
+"""The photometric error maps (include/sfmwarp.h) without a GPU: header, binding and library declare the same two entry
 points and the same descriptor, every documented rejection answers with its code and a message, in the documented order and before
 any HIP call (the pointers are fakes that are never dereferenced), the type errors of torch_api.photometric_error and
 ops.photo_error_*, and the formulas of the header restated in NumPy and checked against the oracle."""
 import ctypes as C
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 from oracle import sfm_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _lib = importlib.import_module("sfm-learner-chainer_amd._lib")
 ops = importlib.import_module("sfm-learner-chainer_amd.ops")
 ta = importlib.import_module("sfm-learner-chainer_amd.torch_api")
 L = _lib.lib
 FAKE = 0x10000                 # never dereferenced
-HEADER = os.path.join(ROOT, "include", "sfmwarp_photo_error.h")
 ENTRY_POINTS = ["sfm_photo_error_bwd", "sfm_photo_error_fwd"]
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
 # header and binding
 # ------------------------------------------------------------------------------------------------------------------------
 def test_header_binding_and_library_declare_the_same_symbols():
-    text = _header()
-    declared = sorted(set(re.findall(r"\b(sfm_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(_lib.PHOTO_ERROR_SYMBOLS) == ENTRY_POINTS
-    others = set(_lib.SYMBOLS) | set(_lib.EXT_SYMBOLS) | set(_lib.INTRINSICS_SYMBOLS) | set(_lib.WARP_PYRAMID_SYMBOLS)
-    assert not set(_lib.PHOTO_ERROR_SYMBOLS) & others
-    assert '#include "sfmwarp.h"' in text and "SFM_ABI_VERSION" not in text
-    for name, (res, args) in _lib.PHOTO_ERROR_SYMBOLS.items():
+    pick = lambda names: sorted(n for n in names if n.startswith("sfm_photo_error"))
+    assert pick(abi_header.declared()) == pick(_lib.SYMBOLS) == ENTRY_POINTS
+    for name in ENTRY_POINTS:
+        res, args = _lib.SYMBOLS[name]
         fn = getattr(L, name)
         assert fn.argtypes == args and fn.restype == res, name
         assert args == [C.POINTER(_lib.SfmPhotoErrorDesc), C.c_void_p] and res is C.c_int
-    assert L.sfm_abi_version() == _lib.SFM_ABI_VERSION == 6
-
-
-def _fields_of_header():
-    """[(name, element size, count)] of SfmPhotoErrorDesc as the header declares it"""
-    body = re.search(r"typedef struct SfmPhotoErrorDesc \{(.*?)\} SfmPhotoErrorDesc;", _header(), flags=re.S).group(1)
-    consts = {"SFM_MAX_SCALES": _lib.SFM_MAX_SCALES, "SFM_MAX_SRC": _lib.SFM_MAX_SRC}
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"(const float \*|float \*|int32_t |float )(.*)$", decl)
-        assert m, decl
-        size = C.sizeof(C.c_void_p) if "*" in m.group(1) else 4
-        for item in m.group(2).split(","):
-            item = item.strip().lstrip("*")
-            a = re.match(r"(\w+)(?:\[(\w+)\])?$", item)
-            assert a, item
-            fields.append((a.group(1), size, consts[a.group(2)] if a.group(2) else 1))
-    return fields
 
 
 def test_descriptor_matches_the_header():
-    fields = _fields_of_header()
-    assert [f[0] for f in fields] == [f[0] for f in _lib.SfmPhotoErrorDesc._fields_]
-    assert [f[0] for f in fields] == ["B", "n_img", "n_scales", "H", "W", "ssim_rate", "img", "tgt", "err", "g_err", "d_img"]
+    abi_header.assert_layout(_lib.SfmPhotoErrorDesc, "SfmPhotoErrorDesc")
+    assert [f[0] for f in abi_header.struct_fields("SfmPhotoErrorDesc")] == ["B", "n_img", "n_scales", "H", "W", "ssim_rate", "img", "tgt", "err",
+                                                                            "g_err", "d_img"]
     assert dict(_lib.SfmPhotoErrorDesc._fields_)["ssim_rate"] is C.c_float
-    off, align = 0, 1
-    for name, size, count in fields:                 # the C layout rule: every member on a multiple of its own size
-        off = -(-off // size) * size
-        assert getattr(_lib.SfmPhotoErrorDesc, name).offset == off, name
-        assert getattr(_lib.SfmPhotoErrorDesc, name).size == size * count, name
-        off += size * count
-        align = max(align, size)
-    assert C.sizeof(_lib.SfmPhotoErrorDesc) == -(-off // align) * align
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -258,7 +219,7 @@ def _pool(a):
 
 
 def emulate(X, Y, alpha, g=None):
-    """err (B,n,h,w) and, with g, d_img (B,n,3,h,w) of include/sfmwarp_photo_error.h in fp64: X (B,n,3,h,w), Y (B,3,h,w)"""
+    """err (B,n,h,w) and, with g, d_img (B,n,3,h,w) of include/sfmwarp.h in fp64: X (B,n,3,h,w), Y (B,3,h,w)"""
     X, Y = np.asarray(X, np.float64), np.asarray(Y, np.float64)[:, None]
     c1, c2 = 1e-4, 9e-4
     mx, my = _pool(X), _pool(Y)

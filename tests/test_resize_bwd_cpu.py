@@ -4,7 +4,6 @@ NumPy emulation of the kernel's arithmetic (tests/resize_bwd_ref.py) meets the f
 dyadic, within the derived tolerance on the edge shapes of tests/test_resize_bwd_gpu.py."""
 import ctypes as C
 import importlib
-import os
 import re
 import subprocess
 
@@ -12,9 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import resize_bwd_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _lib = importlib.import_module("sfm-learner-chainer_amd._lib")
 ops = importlib.import_module("sfm-learner-chainer_amd.ops")
 functions = importlib.import_module("sfm-learner-chainer_amd.functions")
@@ -28,21 +27,15 @@ WHO = "sfm_resize_bwd: "
 # header and binding
 # ------------------------------------------------------------------------------------------------------------------------
 def test_header_and_binding_declare_the_same_symbols():
-    text = open(os.path.join(ROOT, "include", "sfmwarp_ext.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(sfm_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(_lib.EXT_SYMBOLS) == ["sfm_resize_bwd"]
-    assert not set(_lib.EXT_SYMBOLS) & set(_lib.SYMBOLS)
-    assert '#include "sfmwarp.h"' in text
-    assert int(re.search(r"#define SFM_RESIZE_MAX_TERMS (\d+)", text).group(1)) == _lib.SFM_RESIZE_MAX_TERMS == 8
+    assert "sfm_resize_bwd" in abi_header.declared() and "sfm_resize_bwd" in _lib.SYMBOLS
+    assert int(re.search(r"#define SFM_RESIZE_MAX_TERMS (\d+)", abi_header.TEXT).group(1)) == _lib.SFM_RESIZE_MAX_TERMS == 8
 
 
 def test_the_library_exports_them():
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    for name in _lib.EXT_SYMBOLS:
-        assert name in exported, name
-        assert getattr(_lib.lib, name).argtypes == _lib.EXT_SYMBOLS[name][1]
+    assert "sfm_resize_bwd" in exported
+    assert _lib.lib.sfm_resize_bwd.argtypes == _lib.SYMBOLS["sfm_resize_bwd"][1] and _lib.lib.sfm_resize_bwd.restype is C.c_int
 
 
 # ------------------------------------------------------------------------------------------------------------------------

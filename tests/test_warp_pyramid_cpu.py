@@ -1,73 +1,35 @@
-"""The warp of the whole source pyramid (include/sfmwarp_warp_pyramid.h) without a GPU: header, binding and library declare the
+"""The warp of the whole source pyramid (include/sfmwarp.h) without a GPU: header, binding and library declare the
 same three entry points and the same descriptor, every documented rejection answers with its code and a message before any HIP
 call (the pointers are fakes that are never dereferenced), the workspace query, and the type errors of torch_api.warp_pyramid."""
 import ctypes as C
 import importlib
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
+
 _lib = importlib.import_module("sfm-learner-chainer_amd._lib")
 ta = importlib.import_module("sfm-learner-chainer_amd.torch_api")
 L = _lib.lib
 FAKE = 0x10000                 # never dereferenced (256-byte aligned: also a workspace address)
-HEADER = os.path.join(ROOT, "include", "sfmwarp_warp_pyramid.h")
 ENTRY_POINTS = ["sfm_warp_pyramid_bwd", "sfm_warp_pyramid_bwd_workspace_bytes", "sfm_warp_pyramid_fwd"]
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
 # header and binding
 # ------------------------------------------------------------------------------------------------------------------------
 def test_header_binding_and_library_declare_the_same_symbols():
-    text = _header()
-    declared = sorted(set(re.findall(r"\b(sfm_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(_lib.WARP_PYRAMID_SYMBOLS) == ENTRY_POINTS
-    assert not set(_lib.WARP_PYRAMID_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.EXT_SYMBOLS) | set(_lib.INTRINSICS_SYMBOLS))
-    assert '#include "sfmwarp.h"' in text and "SFM_ABI_VERSION" not in text
-    for name, (res, args) in _lib.WARP_PYRAMID_SYMBOLS.items():
+    pick = lambda names: sorted(n for n in names if n.startswith("sfm_warp_pyramid"))
+    assert pick(abi_header.declared()) == pick(_lib.SYMBOLS) == ENTRY_POINTS
+    for name in ENTRY_POINTS:
+        res, args = _lib.SYMBOLS[name]
         fn = getattr(L, name)
         assert fn.argtypes == args and fn.restype == res, name
-    assert L.sfm_abi_version() == _lib.SFM_ABI_VERSION == 6
-
-
-def _fields_of_header():
-    """[(name, element size, count)] of SfmWarpPyramidDesc as the header declares it"""
-    body = re.search(r"typedef struct SfmWarpPyramidDesc \{(.*?)\} SfmWarpPyramidDesc;", _header(), flags=re.S).group(1)
-    consts = {"SFM_MAX_SCALES": _lib.SFM_MAX_SCALES, "SFM_MAX_SRC": _lib.SFM_MAX_SRC}
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"(const float \*|float \*|int32_t )(.*)$", decl)
-        assert m, decl
-        size = 4 if m.group(1).startswith("int32_t") else C.sizeof(C.c_void_p)
-        for item in m.group(2).split(","):
-            item = item.strip().lstrip("*")
-            a = re.match(r"(\w+)(?:\[(\w+)\])?$", item)
-            assert a, item
-            fields.append((a.group(1), size, consts[a.group(2)] if a.group(2) else 1))
-    return fields
 
 
 def test_descriptor_matches_the_header():
-    fields = _fields_of_header()
-    assert [f[0] for f in fields] == [f[0] for f in _lib.SfmWarpPyramidDesc._fields_]
-    off, align = 0, 1
-    for name, size, count in fields:                 # the C layout rule: every member on a multiple of its own size
-        off = -(-off // size) * size
-        assert getattr(_lib.SfmWarpPyramidDesc, name).offset == off, name
-        assert getattr(_lib.SfmWarpPyramidDesc, name).size == size * count, name
-        off += size * count
-        align = max(align, size)
-    assert C.sizeof(_lib.SfmWarpPyramidDesc) == -(-off // align) * align
+    abi_header.assert_layout(_lib.SfmWarpPyramidDesc, "SfmWarpPyramidDesc")
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ H, W, S, N_IMG = 128, 416, 4, 2
 
 
 def aten_photo_error(x, y, alpha):
-    """x (B,n,3,h,w), y (B,3,h,w) -> (B,n,h,w): the formula of include/sfmwarp_photo_error.h in aten"""
+    """x (B,n,3,h,w), y (B,3,h,w) -> (B,n,h,w): the formula of include/sfmwarp.h in aten"""
     B, n, c, h, w = x.shape
     X, Y = x.reshape(B * n, 3, h, w), y[:, None].expand(B, n, 3, h, w).reshape(B * n, 3, h, w)
     l1 = (X - Y).abs().mean(1)
