@@ -15,7 +15,16 @@ from oracle import sfm_oracle as O
 
 # (B, H, W, n_src, n_scales): small; odd sizes, three sources (no pair form); three scales; the reference's smallest scale, four sources
 SHAPES = [(2, 12, 20, 2, 2), (2, 17, 29, 3, 2), (3, 24, 40, 2, 3), (2, 16, 52, 4, 1)]
+# Frames whose tile count per (sample, scale) passes 64, the width of the wave that folds the tiles in proj_bwd_kernel (lane l takes
+# tiles l, l + 64, ...).  Tiles per scale from sfm_loss_plan_info (4-row chunks at these batch sizes; tests/test_fold_rounds_cpu.py
+# pins them):
+#   (2, 264, 60, 2, 2)   66, 33          one strip wide: two lanes go round a second time, and there is a second sample
+#   (2, 128, 208, 3, 1)  128             exactly two full trips; three sources (no pair form)
+#   (1, 128, 416, 2, 4)  224, 64, 16, 4  the workload's own pyramid; scale 1 is the boundary itself
+LARGE_SHAPES = [(2, 264, 60, 2, 2), (2, 128, 208, 3, 1), (1, 128, 416, 2, 4)]
+LARGE_TILES = {LARGE_SHAPES[0]: [66, 33], LARGE_SHAPES[1]: [128], LARGE_SHAPES[2]: [224, 64, 16, 4]}
 KINDS = (None, "skew", "general")
+FAMILIES = {0: "base", 1: "wide", 2: "pair", 3: "ref", 4: "dsrc"}
 CONFIGS = {
     "l1": dict(),
     "ssim_smooth": dict(smooth_reg=0.1, ssim_rate=0.15),
@@ -23,6 +32,53 @@ CONFIGS = {
     "explain": dict(smooth_reg=0.1, exp_reg=0.2),
 }
 SEED = 3
+# (name, shape, mode, layout, projection, want_d_src, the family the gradient launch must be): every kernel family with 66 tiles at
+# scale 0, and the pair and base families on the workload's pyramid (224 tiles at scale 0)
+LARGE_FAMILY_CASES = [
+    ("pair 66 tiles", LARGE_SHAPES[0], "ssim_smooth", "hwc", "fast", False, "pair"),
+    ("base 66 tiles", LARGE_SHAPES[0], "ssim_smooth", "planar", "fast", False, "base"),
+    ("wide 66 tiles", LARGE_SHAPES[0], "l1", "planar", "fast", False, "wide"),
+    ("ref 66 tiles", LARGE_SHAPES[0], "ssim_smooth", "planar", "reference_order", False, "ref"),
+    ("dsrc 66 tiles", LARGE_SHAPES[0], "ssim_smooth", "hwc", "fast", True, "dsrc"),
+    ("pair 224 tiles", LARGE_SHAPES[2], "ssim_smooth", "hwc", "fast", False, "pair"),
+    ("base 224 tiles", LARGE_SHAPES[2], "ssim_smooth", "planar", "fast", False, "base"),
+]
+
+
+def plan_of(lib, desc, grad, loss):
+    """sfm_loss_plan_info of a descriptor whose pointers are bound (any non-NULL value; nothing is launched) for the entry point
+    (grad, loss) -> ([tiles of scale s], family name)"""
+    import ctypes as C
+    n = desc.n_scales
+    out = (C.c_int * (1 + 4 * n + 2))()
+    rc = lib.sfm_loss_plan_info(C.byref(desc), grad, loss, out, len(out))
+    assert rc == 0, rc
+    return [out[4 + 4 * s] for s in range(n)], FAMILIES[out[1 + 4 * n]]
+
+
+def host_plan(shape, mode, layout="planar", projection="fast", want_d_src=False, grad=1, loss=1):
+    """plan_of for the descriptor bind() of tests/test_intrinsics_grad_gpu.py builds for the case, on the host alone: fake pointers
+    that are never dereferenced (as tools/show_plan.py and tests/golden/make_plan_table.py do)"""
+    import importlib
+    _lib = importlib.import_module("sfm-learner-chainer_amd._lib")
+    ops = importlib.import_module("sfm-learner-chainer_amd.ops")
+    B, H, W, n_src, S = shape
+    cfg = dict(smooth_reg=0.0, exp_reg=0.0, ssim_rate=0.0, smooth_mode="second_order")
+    cfg.update(CONFIGS[mode])
+    d = ops.loss_desc(B, B, n_src, [(H >> s, W >> s) for s in range(S)],
+                      (cfg["smooth_reg"], cfg["exp_reg"], cfg["ssim_rate"], _lib.smooth_mode_id(cfg["smooth_mode"]), _lib.projection_id(projection)),
+                      layout)
+    fake = 0x1000
+    d.intrinsics = fake
+    for s in range(S):
+        d.tgt[s] = d.src[s] = d.disp[s] = d.d_disp[s] = fake
+        if cfg["exp_reg"] > 0:
+            d.mask_logits[s] = d.d_mask[s] = fake
+        if want_d_src:
+            d.d_src[s] = fake
+    for i in range(n_src):
+        d.pose[i] = d.d_pose[i] = fake
+    return plan_of(_lib.lib, d, grad, loss)
 
 
 def _ramp(rng, B, G, h_w, lo, hi):
@@ -119,6 +175,15 @@ def worst(got, ref):
     return float(entry_errors(got, ref).max())
 
 
+def proj_entry_errors(got, ref):
+    """the same rule for d_proj (B,S,n,3,4): per scale, source and entry  max_b |got - ref| / max_b |ref|  -> (S,n,3,4)"""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape and got.ndim == 5 and np.isfinite(got).all(), (got.shape, ref.shape)
+    scale = np.abs(ref).max(axis=0)
+    assert (scale > 0).all(), "an entry of the reference gradient is zero in every sample"
+    return np.abs(got - ref).max(axis=0) / scale
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # torch autograd references (tests/test_oracle_vs_torch_cpu.py's restatement of the reference, intrinsics as a leaf)
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -163,8 +228,8 @@ def autograd_loss(d, cfg, dtype="float64", want_gq=False):
 
 @functools.lru_cache(maxsize=None)
 def reference(shape, kind, mode, seed=SEED):
-    """fp64 autograd on the ramp inputs of the case, computed once and shared"""
-    return autograd_loss(ramp_inputs(shape, kind, seed), CONFIGS[mode])
+    """fp64 autograd on the ramp inputs of the case, computed once and shared: d_K, d_poses and d_proj"""
+    return autograd_loss(ramp_inputs(shape, kind, seed), CONFIGS[mode], want_gq=True)
 
 
 def autograd_warp(imgs, depthes, pose, K, g_warped, dtype="float64"):

@@ -3,12 +3,18 @@ differentiated in one launch plus a fold.  The parent's operators -- ops.warp_fw
 are the reference: the forward bit for bit, d_disp to a bound counted in roundings, d_pose against fp64 autograd no worse than
 the per-call route.  No pixel is excluded anywhere.
 
-Shapes (B, H, W, n_src, S): the smallest that reach every index path --
-  (2, 24, 40, 1, 3)  a last scale of 6 x 10 = 60 pixels: less than one wave, one source
-  (2, 20, 52, 3, 2)  1040 pixels = four full blocks + 16, an odd source count
-  (3, 16, 52, 4, 1)  four sources, one scale, B = 3
-each with synth's default motion and with rot_sigma = 0.3, trans_sigma = 0.5 (samples out of view and behind the camera); one also
-with general cameras (tests/cameras.py), so that scale s reads its own K."""
+Shapes (B, H, W, n_src, S), with the 256-pixel blocks per image of every scale.  warp_pyr_fold_kernel adds the block sums of
+one (sample, source, scale) with one wave, lane l taking blocks l, l + 64, ...: only the last shape leaves the first trip of that loop.
+  (2, 24, 40, 1, 3)    4, 1, 1 blocks   a last scale of 6 x 10 = 60 pixels: less than one wave, one source
+  (2, 20, 52, 3, 2)    5, 2 blocks      1040 pixels = four full blocks + 16, an odd source count
+  (3, 16, 52, 4, 1)    4 blocks         four sources, one scale, B = 3
+  (2, 130, 127, 2, 2)  65, 16 blocks    16510 pixels: lane 0 goes round a second time, for a last block of 126 pixels; scale 1 is
+                                        65 x 63 = 4095 pixels, one short of 16 full blocks; a second sample and a second source,
+                                        so that the offsets of both are taken with more than 64 blocks
+The first three with synth's default motion and with rot_sigma = 0.3, trans_sigma = 0.5 (samples out of view and behind the camera),
+the last with the default motion; the second and the last also with general cameras (tests/cameras.py), so that scale s reads its
+own K.  tests/test_fold_rounds_cpu.py pins the block counts and shows that the fp64 reference of d_pose moves by far more than the
+tolerances here when the pixels beyond the first 64 blocks are left out."""
 import ctypes as C
 import functools
 import importlib
@@ -27,9 +33,12 @@ ops = importlib.import_module("sfm-learner-chainer_amd.ops")
 synth = importlib.import_module("sfm-learner-chainer_amd.synth")
 ta = importlib.import_module("sfm-learner-chainer_amd.torch_api")
 
-SHAPES = [(2, 24, 40, 1, 3), (2, 20, 52, 3, 2), (3, 16, 52, 4, 1)]
+SHAPES = [(2, 24, 40, 1, 3), (2, 20, 52, 3, 2), (3, 16, 52, 4, 1), (2, 130, 127, 2, 2)]
+FOLD_SHAPE = SHAPES[3]                             # more than 64 blocks at scale 0
 LARGE = dict(rot_sigma=0.3, trans_sigma=0.5)
-CASES = [(shape, motion, None) for shape in SHAPES for motion in ("default", "large")] + [(SHAPES[1], "default", "general")]
+CASES = [(shape, motion, None) for shape in SHAPES[:3] for motion in ("default", "large")] + [(SHAPES[1], "default", "general")]
+FOLD_CASES = [(FOLD_SHAPE, "default", None), (FOLD_SHAPE, "default", "general")]
+CASES += FOLD_CASES                                # (appended: the tests below name earlier cases by index)
 IDS = ["%s-%s%s" % ("x".join(map(str, s)), m, "-" + k if k else "") for s, m, k in CASES]
 F64 = np.float64
 DEV = "cuda:0"
@@ -53,18 +62,27 @@ def _t(a):
 
 
 @functools.lru_cache(maxsize=None)
-def case(shape, motion, kind):
-    """Everything the tests of one case share, computed once (never modify it): the inputs, the new route's outputs in both
-    layouts, and the parent's per-(scale, source) operators on the same inputs."""
+def host_case(shape, motion, kind):
+    """the inputs of one case on the host (never modify them): synth's arrays `d` and the upstream gradients `g`"""
     B, H, W, n, S = shape
     seed = 11 + SHAPES.index(shape)
     d = synth.make_inputs(B=B, H=H, W=W, n_src=n, n_scales=S, seed=seed, **(LARGE if motion == "large" else {}))
     d = cameras.with_cameras(d, kind, 1000 + seed)
+    gen = torch.Generator().manual_seed(100 + seed)
+    return dict(d=d, shape=shape, g=[torch.randn((B, n, 3, H >> s, W >> s), generator=gen) for s in range(S)])
+
+
+@functools.lru_cache(maxsize=None)
+def case(shape, motion, kind):
+    """Everything the tests of one case share, computed once (never modify it): the inputs, the new route's outputs in both
+    layouts, and the parent's per-(scale, source) operators on the same inputs."""
+    B, H, W, n, S = shape
+    h = host_case(shape, motion, kind)
+    d = h["d"]
     x = dict(d=d, shape=shape, planar=[_t(a) for a in d["src_pyr"]], disps=[_t(a) for a in d["disps"]], poses=[_t(a) for a in d["poses"]],
              K=_t(d["intrinsics"]))
     x["hwc"] = [ops.to_hwc(a) for a in x["planar"]]
-    gen = torch.Generator().manual_seed(100 + seed)
-    x["g"] = [torch.randn((B, n, 3, H >> s, W >> s), generator=gen).to(DEV) for s in range(S)]
+    x["g"] = [g.to(DEV) for g in h["g"]]
     for layout in ("planar", "hwc"):
         x["warped_" + layout], x["valid_" + layout] = ops.warp_pyramid_fwd(x[layout], x["disps"], x["poses"], x["K"], layout, want_valid=True)
         x["bwd_" + layout] = ops.warp_pyramid_bwd(x[layout], x["disps"], x["poses"], x["K"], layout, x["g"])
@@ -139,9 +157,10 @@ def test_d_disp_within_its_counted_roundings(shape, motion, kind):
 # ------------------------------------------------------------------------------------------------------------------------
 # 3. d_pose
 # ------------------------------------------------------------------------------------------------------------------------
-def _autograd_d_pose(x):
+def _autograd_d_pose(x, first_pixels=None):
     """fp64 autograd of the torch restatement of projective_inverse_warp (tests/test_oracle_vs_torch_cpu.py, switched to fp64 the way
-    tests/intrinsics_grad.py::autograd_warp does), summed over the scales: d_pose per source"""
+    tests/intrinsics_grad.py::autograd_warp does), summed over the scales: d_pose per source.  x: a case or a host_case.
+    first_pixels: the upstream gradient counts only on pixels j < first_pixels of every image (tests/test_fold_rounds_cpu.py)"""
     import test_oracle_vs_torch_cpu as T
     d = x["d"]
     B, H, W, n, S = x["shape"]
@@ -155,7 +174,10 @@ def _autograd_d_pose(x):
             depth = (1.0 / t(d["disps"][s])).reshape(B, 1, -1).expand(B, 3, -1)
             for i in range(n):
                 out = T.projective_inverse_warp(t(d["src_pyr"][s][:, 3 * i:3 * i + 3]), depth, poses[i], t(d["intrinsics"][:, s]))
-                total = total + (out * t(x["g"][s][:, i].cpu().numpy())).sum()
+                g = x["g"][s][:, i].cpu().numpy().astype(F64)
+                if first_pixels is not None:
+                    g.reshape(B, 3, -1)[:, :, first_pixels:] = 0
+                total = total + (out * t(g)).sum()
         total.backward()
     finally:
         T.DT = saved
@@ -192,19 +214,22 @@ def test_d_pose_no_worse_than_the_per_call_route(shape, motion, kind):
 # ------------------------------------------------------------------------------------------------------------------------
 # 4. determinism and buffers
 # ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("layout", ["planar", "hwc"])
-def test_two_backward_calls_agree_bit_for_bit(layout):
-    x = case(*CASES[3])
+@pytest.mark.parametrize("layout,which", [("planar", 3), ("hwc", 3), ("planar", CASES.index(FOLD_CASES[1])), ("hwc", CASES.index(FOLD_CASES[1]))],
+                         ids=["planar", "hwc", "planar-65_blocks", "hwc-65_blocks"])
+def test_two_backward_calls_agree_bit_for_bit(layout, which):
+    x = case(*CASES[which])
     d_disps, d_poses = ops.warp_pyramid_bwd(x[layout], x["disps"], x["poses"], x["K"], layout, x["g"])
     for a, b in zip(d_disps + d_poses, x["bwd_" + layout][0] + x["bwd_" + layout][1]):
         assert _bits(a, b)
 
 
-@pytest.mark.parametrize("layout,res", [("planar", 0), ("hwc", 4), ("hwc", 12)])
-def test_buffer_contract(dev, layout, res):
+@pytest.mark.parametrize("layout,res,which", [("planar", 0, 2), ("hwc", 4, 2), ("hwc", 12, 2), ("hwc", 4, CASES.index(FOLD_CASES[0]))],
+                         ids=["planar-0", "hwc-4", "hwc-12", "hwc-4-65_blocks"])
+def test_buffer_contract(dev, layout, res, which):
     """every output pre-filled with the sentinel is overwritten completely, inputs are only read, and the guard bands around warped,
-    valid, d_disp, d_pose and the workspace stay as they were; placed at `res` bytes off a 16-byte boundary"""
-    x = case(*CASES[2])
+    valid, d_disp, d_pose and the workspace stay as they were; placed at `res` bytes off a 16-byte boundary.  The workspace starts
+    out as NaN sentinels: a fold that reads a block sum nobody wrote (the 65-block case takes its second trip) gives a NaN d_pose"""
+    x = case(*CASES[which])
     B, H, W, n, S = x["shape"]
     hw = [(H >> s, W >> s) for s in range(S)]
     d = _lib.SfmWarpPyramidDesc()
