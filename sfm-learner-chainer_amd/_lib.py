@@ -86,6 +86,27 @@ class SfmPhotoErrorDesc(C.Structure):
     ]
 
 
+MIN_REPROJ_NORM_KEPT, MIN_REPROJ_NORM_ALL = 0, 1
+MIN_REPROJ_NORMS = {"kept": MIN_REPROJ_NORM_KEPT, "all": MIN_REPROJ_NORM_ALL}
+
+
+def min_reproj_norm_id(name):
+    """SFM_MIN_REPROJ_NORM_* of a `norm` argument; anything outside the table is a ValueError"""
+    return _setting(MIN_REPROJ_NORMS, "norm", name)
+
+
+class SfmMinReprojDesc(C.Structure):      # include/sfmwarp_min_reproj.h
+    _fields_ = [
+        ("B", C.c_int32), ("n_err", C.c_int32), ("n_ident", C.c_int32), ("n_scales", C.c_int32),
+        ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
+        ("norm", C.c_int32), ("weight", C.c_float * SFM_MAX_SCALES),
+        ("err", _FP * SFM_MAX_SCALES), ("valid", _FP * SFM_MAX_SCALES), ("ident", _FP * SFM_MAX_SCALES),
+        ("winner", C.c_void_p * SFM_MAX_SCALES),      # device int8_t*
+        ("loss", _FP), ("count", C.c_void_p), ("g_loss", _FP),      # count: device int32_t*
+        ("g_err", _FP * SFM_MAX_SCALES),
+    ]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -138,6 +159,13 @@ SYMBOLS = {
     "sfm_photo_error_bwd": (_I, [C.POINTER(SfmPhotoErrorDesc), _V]),
 }
 
+# every symbol declared in the side header include/sfmwarp_min_reproj.h (to be folded into SYMBOLS together with that header)
+EXT_SYMBOLS = {
+    "sfm_min_reproj_workspace_bytes": (_Z, [C.POINTER(SfmMinReprojDesc)]),
+    "sfm_min_reproj_fwd": (_I, [C.POINTER(SfmMinReprojDesc), _V, _Z, _V]),
+    "sfm_min_reproj_bwd": (_I, [C.POINTER(SfmMinReprojDesc), _V]),
+}
+
 
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
@@ -149,7 +177,7 @@ def _load():
             "libsfmwarp.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -9,11 +9,11 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SfmLossDesc, SfmPhotoErrorDesc, SfmWarpPyramidDesc, check, lib
+from ._lib import SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpPyramidDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
-           "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd"]
+           "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "min_reproj_fwd", "min_reproj_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -357,7 +357,7 @@ def layout_for(H, W):
 
 
 def _set_scales(d, hw):
-    """n_scales, H[] and W[] of any of the three descriptors from hw = [(h, w) of each scale]"""
+    """n_scales, H[] and W[] of any of the four descriptors from hw = [(h, w) of each scale]"""
     d.n_scales = len(hw)
     for s, (h, w) in enumerate(hw):
         d.H[s], d.W[s] = h, w
@@ -576,6 +576,102 @@ def photo_error_bwd(imgs, tgts, ssim_rate, g_err):
         _point(field, arrays)
     _launch(dev, lib.sfm_photo_error_bwd, C.byref(d))
     return d_imgs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the minimum over the sources, the auto-mask and the mean of every scale (include/sfmwarp_min_reproj.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _min_reproj_desc(B, n_err, n_ident, hw, weights, norm):
+    """An SfmMinReprojDesc with every non-pointer field set.  norm: "kept" or "all"; weights: one non-negative number per scale"""
+    if len(weights) != len(hw) or not 1 <= len(hw) <= _lib.SFM_MAX_SCALES:
+        raise TypeError("one weight per scale (1..%d), got %d weights for %d scales" % (_lib.SFM_MAX_SCALES, len(weights), len(hw)))
+    d = SfmMinReprojDesc()
+    d.B, d.n_err, d.n_ident, d.norm = B, n_err, n_ident, _lib.min_reproj_norm_id(norm)
+    _set_scales(d, hw)
+    for s, w in enumerate(weights):
+        d.weight[s] = float(w)
+    return d
+
+
+def min_reproj_fwd(errs, valids, idents, weights, norm):
+    """Per pixel the smallest error over the sources, the auto-mask and the mean of every scale in two launches
+    (sfm_min_reproj_fwd): errs[s] (B,n_err,h,w) -- what `photo_error_fwd` returns for the warped pyramid --, valids None or a list
+    with (B,n_err,h,w) or None per scale (sources with valid <= 0 at a pixel do not compete), idents None (no auto-mask) or
+    [(B,n_ident,h,w)], the errors of the unwarped sources: a pixel is kept where some valid source has a finite error that is
+    strictly below every ident.  weights: one per scale; norm: "kept" (the mean over the kept pixels) or "all" (over all pixels).
+    -> (loss (S+1,) float32: the mean of each scale and, last, their weighted sum; count (S,) int32: the kept pixels;
+    [winner_s (B,h,w) int8]: the index of the source a kept pixel took its error from, else -1).  No atomics: the same bits on
+    every call.  A rejection by the library (a negative weight) is a ValueError with sfm_last_error() as its message."""
+    if not isinstance(errs, (list, tuple)) or not 1 <= len(errs) <= _lib.SFM_MAX_SCALES:
+        raise TypeError("errs must be a list with one array per scale (1..%d)" % _lib.SFM_MAX_SCALES)
+    S = len(errs)
+    errs = _devs(errs, "errs", 4)
+    B, n_err = errs[0].shape[:2]
+    dev = errs[0].device
+    if not 1 <= n_err <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d error maps per sample, got %d" % (_lib.SFM_MAX_SRC, n_err))
+    hw = [tuple(t.shape[2:]) for t in errs]
+    valids = [None] * S if valids is None else list(valids)
+    if len(valids) != S or (idents is not None and len(idents) != S):
+        raise TypeError("valids and idents need one entry per scale")
+    valids = [None if t is None else _dev(t, "valids[%d]" % s, 4) for s, t in enumerate(valids)]
+    idents = [] if idents is None else _devs(idents, "idents", 4)
+    n_ident = idents[0].shape[1] if idents else 0
+    if idents and not 1 <= n_ident <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d identity maps per sample, got %d" % (_lib.SFM_MAX_SRC, n_ident))
+    for s, (h, w) in enumerate(hw):
+        if tuple(errs[s].shape) != (B, n_err, h, w) or (valids[s] is not None and valids[s].shape != errs[s].shape):
+            raise TypeError("scale %d: errs and valids must be (B,n_err,h,w) = %s" % (s, (B, n_err, h, w)))
+        if idents and tuple(idents[s].shape) != (B, n_ident, h, w):
+            raise TypeError("idents[%d] must be (B,n_ident,h,w) = %s, got %s" % (s, (B, n_ident, h, w), tuple(idents[s].shape)))
+    _one_device(dev, errs + [t for t in valids if t is not None] + idents)
+    d = _min_reproj_desc(B, n_err, n_ident, hw, weights, norm)
+    loss = torch.empty((S + 1,), dtype=torch.float32, device=dev)
+    count = torch.empty((S,), dtype=torch.int32, device=dev)
+    winners = [torch.empty((B, h, w), dtype=torch.int8, device=dev) for h, w in hw]
+    for field, arrays in ((d.err, errs), (d.valid, valids), (d.ident, idents), (d.winner, winners)):
+        _point(field, arrays)
+    d.loss, d.count = loss.data_ptr(), count.data_ptr()
+    if B == 0:      # the mean of nothing, as the library defines it for a scale with nothing kept; nothing to launch
+        return loss.zero_(), count.zero_(), winners
+    nbytes = lib.sfm_min_reproj_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        check(lib.sfm_min_reproj_fwd(C.byref(d), None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid min reprojection descriptor")
+    ws, ptr, have = _place_workspace(None, nbytes, dev)
+    _launch(dev, lib.sfm_min_reproj_fwd, C.byref(d), C.c_void_p(ptr), have)
+    return loss, count, winners
+
+
+def min_reproj_bwd(winners, count, g_loss, n_err, weights, norm, shapes):
+    """The backward of `min_reproj_fwd` for the upstream gradients g_loss (S+1,) of its `loss`, ONE launch (sfm_min_reproj_bwd):
+    winners and count as the forward returned them, shapes = [(h, w)] -> [g_err_s (B,n_err,h,w)], c_s at the winning source of a
+    kept pixel and 0 everywhere else, c_s = (g_loss[s] + weights[s] * g_loss[S]) / denom[s].  The kernel reads count and g_loss on
+    the device: nothing syncs."""
+    hw = [tuple(x) for x in shapes]
+    S = len(hw)
+    if not isinstance(winners, (list, tuple)) or len(winners) != S or not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("winners and shapes need one entry per scale (1..%d)" % _lib.SFM_MAX_SCALES)
+    if not 1 <= int(n_err) <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d error maps per sample, got %d" % (_lib.SFM_MAX_SRC, n_err))
+    g_loss = _dev(g_loss, "g_loss", 1)
+    dev = g_loss.device
+    B = winners[0].shape[0] if isinstance(winners[0], torch.Tensor) and winners[0].dim() == 3 else -1
+    for s, (t, (h, w)) in enumerate(zip(winners, hw)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int8 or tuple(t.shape) != (B, h, w) or not t.is_contiguous():
+            raise TypeError("winners[%d] must be a contiguous int8 array (B,h,w) = %s" % (s, (B, h, w)))
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or tuple(count.shape) != (S,) or not count.is_contiguous():
+        raise TypeError("count must be a contiguous int32 array (%d,)" % S)
+    if tuple(g_loss.shape) != (S + 1,):
+        raise TypeError("g_loss must be (%d,), got %s" % (S + 1, tuple(g_loss.shape)))
+    _one_device(dev, list(winners) + [count])
+    d = _min_reproj_desc(B, int(n_err), 0, hw, weights, norm)
+    g_errs = _empty([(B, int(n_err), h, w) for h, w in hw], dev)
+    for field, arrays in ((d.winner, winners), (d.g_err, g_errs)):
+        _point(field, arrays)
+    d.count, d.g_loss = count.data_ptr(), g_loss.data_ptr()
+    _launch(dev, lib.sfm_min_reproj_bwd, C.byref(d))
+    return g_errs
 
 
 class FusedLoss:

@@ -9,6 +9,9 @@ grad_fn.  This module hands those outputs to libsfmwarp and the gradients it com
                                       loss of the caller's own (ops.pyramid_hwc, ops.warp_pyramid_fwd / ops.warp_pyramid_bwd)
   photometric_error                   alpha * SSIM + (1 - alpha) * L1 per pixel (models/base_model.py:96,126-142) of every (scale, image) of
                                       a step, differentiable w.r.t. the images (ops.photo_error_fwd / ops.photo_error_bwd)
+  min_reprojection                    the stage behind it: per pixel the minimum over the sources, the auto-mask against the unwarped
+                                      sources and the mean of every scale (ops.min_reproj_fwd / ops.min_reproj_bwd)
+  min_reprojection_loss               warp_pyramid -> photometric_error -> min_reprojection as one call and ONE autograd node
   multi_scale_intrinsics              datasets/kitti/kitti_raw_transformed.py:76-93, differentiable (plain torch)
   disp_activation                     models/disp_net.py:104-122 (ops.disp_act_fwd / ops.disp_act_bwd)
   resize_images / resize_like         F.resize_images as DispNet's decoder differentiates it, models/disp_net.py:11-14,105,111,117
@@ -39,7 +42,8 @@ from . import _lib, ops
 from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
-           "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error"]
+           "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error",
+           "min_reprojection", "min_reprojection_loss"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -635,6 +639,144 @@ def photometric_error(imgs, tgt, *, ssim_rate):
         if x.device != xs[0].device or y.device != xs[0].device:
             raise TypeError("every array must live on %s" % (xs[0].device,))
     return list(_PhotoError.apply(float(ssim_rate), S, *xs, *[y.detach() for y in tgts]))
+
+
+def _scale_weights(weights, S):
+    """`weights` of min_reprojection / min_reprojection_loss as a tuple of S floats; None: 2**-s, the example of INTEGRATION.md"""
+    if weights is None:
+        return tuple(2.0 ** -s for s in range(S))
+    weights = tuple(float(w) for w in weights)
+    if len(weights) != S:
+        raise TypeError("weights: one per scale, got %d for %d scales" % (len(weights), S))
+    return weights
+
+
+def _g_loss(S, g_total, g_scales, device):
+    """(S+1,) float32: the upstream gradients of (per_scale, total) as sfm_min_reproj_bwd reads them; None is zero.  On the device."""
+    total = torch.zeros((1,), dtype=torch.float32, device=device) if g_total is None else g_total.to(torch.float32).reshape(1)
+    if g_scales is None:
+        return torch.nn.functional.pad(total, (S, 0))
+    return torch.cat([g_scales.to(torch.float32).reshape(S), total])
+
+
+class _MinReproj(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, weights, norm, bound, has_ident, *arrays):
+        errs, rest = list(arrays[:S]), list(arrays[S:])
+        valids = [rest.pop(0) if on else None for on in bound]
+        idents = rest if has_ident else None
+        loss, count, winners = ops.min_reproj_fwd(errs, valids, idents, weights, norm)
+        ctx.save_for_backward(count, *winners)
+        ctx.cfg = (S, errs[0].shape[1], weights, norm, [tuple(e.shape[2:]) for e in errs], len(arrays))
+        ctx.mark_non_differentiable(*winners)
+        ctx.set_materialize_grads(False)
+        return (loss[S], loss[:S]) + tuple(winners)
+
+    @staticmethod
+    def backward(ctx, g_total, g_scales, *_):
+        S, n_err, weights, norm, hw, n_arrays = ctx.cfg
+        if g_total is None and g_scales is None:
+            return (None,) * (5 + n_arrays)
+        count, winners = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+        g_errs = ops.min_reproj_bwd(winners, count, _g_loss(S, g_total, g_scales, count.device), n_err, weights, norm, hw)
+        return (None,) * 5 + tuple(g_errs) + (None,) * (n_arrays - S)
+
+
+def min_reprojection(errs, *, valid=None, ident=None, weights=None, norm="kept"):
+    """The last stage of a Monodepth2-style loss on the library's warp: per pixel the smallest error over the sources, the
+    auto-mask against the unwarped sources and the mean, every scale in two launches (ops.min_reproj_fwd) and one backward
+    (ops.min_reproj_bwd) -- what the examples of INTEGRATION.md spell as where / min / < / where / sum / sum / clamp / divide per scale.
+
+    errs: a list of S tensors (B,n,h_s,w_s) -- what `photometric_error` returns for the list `warp_pyramid` returns; float32,
+      bfloat16 or float16 on a ROCm device (computed in float32, the gradient returned in the input's dtype);
+    valid: None, or a list of S entries, each (B,n,h_s,w_s) float32 or None -- `warp_pyramid(..., return_valid=True)`: a source with
+      valid <= 0 at a pixel does not compete there;
+    ident: None (no auto-mask) or a list of S tensors (B,m,h_s,w_s) float32, the errors of the unwarped sources: a pixel counts only
+      where its smallest error is strictly below every one of them;
+    weights: one per scale, default 2**-s; norm: "kept" -- each scale's mean runs over its kept pixels (at least 1) -- or "all" -- over
+      all B*h*w pixels, Monodepth2's own `.mean()`.
+
+    Returns (total, per_scale, winners): total, 0-d, = sum_s weights[s] * per_scale[s]; per_scale (S,), the mean of each scale; both
+    differentiable with respect to `errs` ONLY (valid and ident are constants); winners, a list of S int8 maps (B,h_s,w_s): the source a
+    kept pixel took its error from, -1 where the pixel is dropped.  A NaN or +inf error never wins.  Sums run in fp64 in a fixed
+    order: the same bits on every call.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture."""
+    if not isinstance(errs, (list, tuple)):
+        raise TypeError("errs must be a list of (B,n,h,w) tensors, one per scale")
+    S = len(errs)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
+    xs = [_dev_float(t, "errs[%d]" % s, 4) for s, t in enumerate(errs)]
+    valid = [None] * S if valid is None else list(valid)
+    if len(valid) != S or (ident is not None and len(ident) != S):
+        raise TypeError("valid and ident need one entry per scale (%d)" % S)
+    bound = tuple(v is not None for v in valid)
+    vs = [ops._dev(v, "valid[%d]" % s, 4).detach() for s, v in enumerate(valid) if v is not None]
+    ids = [] if ident is None else [t.detach() for t in ops._devs(ident, "ident", 4)]
+    out = _MinReproj.apply(S, _scale_weights(weights, S), norm, bound, ident is not None, *xs, *vs, *ids)
+    return out[0], out[1], list(out[2:])
+
+
+class _MinReprojLoss(torch.autograd.Function):
+    """warp_pyramid -> photometric_error -> min_reprojection as ONE node: the six launches of the forward and the four of the
+    backward run back to back from one `apply`, and autograd's engine visits one node with S + n_src leaves behind it."""
+
+    @staticmethod
+    def forward(ctx, tgt, src, K, cfg, S, *arrays):
+        ssim_rate, auto_mask, weights, norm = cfg
+        disps, poses = list(arrays[:S]), list(arrays[S:])
+        B, n_src = src.shape[0], len(poses)
+        pyr = ops.pyramid_hwc(src, S)
+        warped, valid = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", True)
+        tgts = ops.pyramid(tgt, S)
+        errs = ops.photo_error_fwd(warped, tgts, ssim_rate)
+        idents = None
+        if auto_mask:     # the identity reprojection: the planar source pyramid is (B,n_src,3,h,w) byte for byte
+            idents = ops.photo_error_fwd([p.view(B, n_src, 3, p.shape[2], p.shape[3]) for p in ops.pyramid(src, S)], tgts, ssim_rate)
+        loss, count, winners = ops.min_reproj_fwd(errs, valid, idents, weights, norm)
+        ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners)
+        ctx.cfg = (S, n_src, ssim_rate, weights, norm)
+        return loss[S]
+
+    @staticmethod
+    def backward(ctx, g_total):
+        S, n_src, ssim_rate, weights, norm = ctx.cfg
+        if g_total is None:
+            return (None,) * (5 + S + n_src)
+        K, count, rest = ctx.saved_tensors[0], ctx.saved_tensors[1], list(ctx.saved_tensors[2:])
+        pyr, disps, poses = rest[:S], rest[S:2 * S], rest[2 * S:2 * S + n_src]
+        rest = rest[2 * S + n_src:]
+        warped, tgts, winners = rest[:S], rest[S:2 * S], rest[2 * S:]
+        g_errs = ops.min_reproj_bwd(winners, count, _g_loss(S, g_total, None, count.device), n_src, weights, norm,
+                                    [tuple(t.shape[2:]) for t in disps])
+        d_warped = ops.photo_error_bwd(warped, tgts, ssim_rate, g_errs)
+        d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", d_warped)
+        return (None,) * 5 + tuple(d_disps) + tuple(d_poses)
+
+
+def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, *, ssim_rate, auto_mask=True, weights=None, norm="kept"):
+    """The Monodepth2-style loss of INTEGRATION.md ("Your own loss on the library's warp") in one call and ONE autograd node: per
+    pixel the smallest ssim_rate * SSIM + (1 - ssim_rate) * L1 error over the warped sources that are in view, averaged per scale
+    over the pixels where it is strictly below the error of every UNWARPED source (`auto_mask`; off: over the pixels some source
+    sees), the scales added with `weights` (default 2**-s).
+
+    The inputs are those of `sfm_learner_loss`: tgt_img (B,3,H,W) and src_imgs (B,n_src,3,H,W) float32, constants; intrinsics
+    (B,S,3,3), a constant HERE as in `warp_pyramid` (TypeError if it requires grad); pred_disps: S tensors (B,1,H>>s,W>>s);
+    pred_poses: n_src tensors (B,6) or one packed (B,6*n_src) tensor -- float32, bfloat16 or float16, each gradient returned in its
+    input's dtype.  norm: "kept" or "all", as in `min_reprojection`.
+
+    Returns total (0-d).  Forward: the source pyramid, `warp_pyramid`'s launch with its valid masks, the target pyramid,
+    `photometric_error`'s launch on the warped pyramid and, with `auto_mask`, on the unwarped one, `min_reprojection`'s two.  Backward:
+    one launch each of min_reprojection, photometric_error and the warp, plus the warp's small fold.  The values are those of the three
+    stages called one after the other, bit for bit; nothing reads a device value on the host, so the step can be captured in a graph."""
+    tgt = ops._dev(tgt_img, "tgt_img", 4)
+    src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt)
+    if K.requires_grad:
+        raise TypeError("min_reprojection_loss does not differentiate the intrinsics: detach them")
+    B, n_src, _, H, W = src.shape
+    S = len(disps)
+    cfg = (float(ssim_rate), bool(auto_mask), _scale_weights(weights, S), norm)
+    _lib.min_reproj_norm_id(norm)
+    return _MinReprojLoss.apply(tgt.detach(), src.detach().view(B, 3 * n_src, H, W), K, cfg, S, *disps, *poses)
 
 
 def multi_scale_intrinsics(K, n_scales):
