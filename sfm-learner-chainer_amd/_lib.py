@@ -107,6 +107,26 @@ class SfmMinReprojDesc(C.Structure):      # include/sfmwarp_min_reproj.h
     ]
 
 
+DISP_SMOOTH_EDGE_MEAN_ABS, DISP_SMOOTH_EDGE_ABS_MEAN = 0, 1
+DISP_SMOOTH_EDGES = {"mean_abs": DISP_SMOOTH_EDGE_MEAN_ABS, "abs_mean": DISP_SMOOTH_EDGE_ABS_MEAN}
+
+
+def disp_smooth_edge_id(name):
+    """SFM_DISP_SMOOTH_EDGE_* of an `edge` argument; anything outside the table is a ValueError"""
+    return _setting(DISP_SMOOTH_EDGES, "edge", name)
+
+
+class SfmDispSmoothDesc(C.Structure):     # include/sfmwarp_disp_smooth.h
+    _fields_ = [
+        ("B", C.c_int32), ("n_scales", C.c_int32),
+        ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
+        ("normalize", C.c_int32), ("edge", C.c_int32), ("accumulate", C.c_int32), ("weight", C.c_float * SFM_MAX_SCALES),
+        ("disp", _FP * SFM_MAX_SCALES), ("img", _FP * SFM_MAX_SCALES),
+        ("loss", _FP), ("stats", C.c_void_p), ("g_loss", _FP),      # stats: device double*
+        ("g_disp", _FP * SFM_MAX_SCALES),
+    ]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -167,6 +187,14 @@ EXT_SYMBOLS = {
 }
 
 
+# every symbol declared in the side header include/sfmwarp_disp_smooth.h (to be folded into SYMBOLS together with that header)
+SMOOTH_SYMBOLS = {
+    "sfm_disp_smooth_workspace_bytes": (_Z, [C.POINTER(SfmDispSmoothDesc)]),
+    "sfm_disp_smooth_fwd": (_I, [C.POINTER(SfmDispSmoothDesc), _V, _Z, _V]),
+    "sfm_disp_smooth_bwd": (_I, [C.POINTER(SfmDispSmoothDesc), _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -177,7 +205,7 @@ def _load():
             "libsfmwarp.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SMOOTH_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -9,11 +9,12 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpPyramidDesc, check, lib
+from ._lib import SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpPyramidDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
-           "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "min_reproj_fwd", "min_reproj_bwd"]
+           "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "min_reproj_fwd", "min_reproj_bwd",
+           "disp_smooth_fwd", "disp_smooth_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -672,6 +673,90 @@ def min_reproj_bwd(winners, count, g_loss, n_err, weights, norm, shapes):
     d.count, d.g_loss = count.data_ptr(), g_loss.data_ptr()
     _launch(dev, lib.sfm_min_reproj_bwd, C.byref(d))
     return g_errs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the edge-aware smoothness of the (mean-normalised) disparity of every scale (include/sfmwarp_disp_smooth.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _disp_smooth_desc(disps, tgts, weights, normalize, edge):
+    """(descriptor with the inputs and every setting bound, the arrays it points at, B, [(h, w)], device) for disp_smooth_fwd / _bwd"""
+    if not isinstance(disps, (list, tuple)) or not isinstance(tgts, (list, tuple)):
+        raise TypeError("disps and tgts must be lists with one array per scale")
+    S = len(disps)
+    if len(tgts) != S or not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("disps and tgts need one entry per scale (1..%d), got %d and %d" % (_lib.SFM_MAX_SCALES, S, len(tgts)))
+    if len(weights) != S:
+        raise TypeError("one weight per scale (1..%d), got %d weights for %d scales" % (_lib.SFM_MAX_SCALES, len(weights), S))
+    disps, tgts = _devs(disps, "disps", 4), _devs(tgts, "tgts", 4)
+    B, dev = disps[0].shape[0], disps[0].device
+    hw = [tuple(t.shape[2:]) for t in disps]
+    for s, (h, w) in enumerate(hw):
+        if tuple(disps[s].shape) != (B, 1, h, w) or tuple(tgts[s].shape) != (B, 3, h, w):
+            raise TypeError("scale %d: expected disps (B,1,h,w) = %s and tgts (B,3,h,w), got %s and %s"
+                            % (s, (B, 1, h, w), tuple(disps[s].shape), tuple(tgts[s].shape)))
+    _one_device(dev, disps + tgts)
+    d = SfmDispSmoothDesc()
+    d.B, d.normalize, d.edge = B, int(bool(normalize)), _lib.disp_smooth_edge_id(edge)
+    _set_scales(d, hw)
+    for s, w in enumerate(weights):
+        d.weight[s] = float(w)
+    for field, arrays in ((d.disp, disps), (d.img, tgts)):
+        _point(field, arrays)
+    return d, (disps, tgts), B, hw, dev
+
+
+def disp_smooth_fwd(disps, tgts, weights, normalize, edge):
+    """The edge-aware smoothness of the disparity of every scale in two launches (sfm_disp_smooth_fwd): disps[s] (B,1,h,w),
+    tgts[s] (B,3,h,w) planar, the images whose edges relax the penalty; weights: one per scale; normalize: divide each sample's
+    disparity by its own mean + 1e-7 first (Monodepth2) -- done by factoring |M_b| out of the sums, in the same pass; edge:
+    "mean_abs" (exp(-mean_c |dI|), Monodepth2) or "abs_mean" (exp(-|mean_c dI|), compute_disp_smooth of models/base_model.py:144-155).
+    -> (loss (S+1,) float32: mean_x + mean_y of each scale and, last, their weighted sum; stats (S,B,3) float64: per (scale, sample)
+    M_b, X_b, Y_b of the header, which `disp_smooth_bwd` reads).  No atomics: the same bits on every call.  A rejection by the library
+    (a negative weight) is a ValueError with sfm_last_error() as its message."""
+    d, keep, B, hw, dev = _disp_smooth_desc(disps, tgts, weights, normalize, edge)
+    S = len(hw)
+    loss = torch.empty((S + 1,), dtype=torch.float32, device=dev)
+    stats = torch.empty((S, B, 3), dtype=torch.float64, device=dev)
+    d.loss, d.stats = loss.data_ptr(), stats.data_ptr()
+    if B == 0:      # the sum over no samples; nothing to launch
+        return loss.zero_(), stats
+    nbytes = lib.sfm_disp_smooth_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        check(lib.sfm_disp_smooth_fwd(C.byref(d), None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid disparity smoothness descriptor")
+    ws, ptr, have = _place_workspace(None, nbytes, dev)
+    _launch(dev, lib.sfm_disp_smooth_fwd, C.byref(d), C.c_void_p(ptr), have)
+    return loss, stats
+
+
+def disp_smooth_bwd(disps, tgts, stats, g_loss, weights, normalize, edge, out=None):
+    """The backward of `disp_smooth_fwd` for the upstream gradients g_loss (S+1,) of its `loss`, ONE launch (sfm_disp_smooth_bwd):
+    stats as the forward returned it -> [g_disp_s (B,1,h,w)].  With `out`, a list of S contiguous float32 arrays (B,1,h,w), the
+    gradient is ADDED to them in place (one fp32 addition per element) and they are returned.  The images get no gradient.  The kernel
+    reads stats and g_loss on the device: nothing syncs."""
+    d, keep, B, hw, dev = _disp_smooth_desc(disps, tgts, weights, normalize, edge)
+    S = len(hw)
+    g_loss = _dev(g_loss, "g_loss", 1)
+    if tuple(g_loss.shape) != (S + 1,):
+        raise TypeError("g_loss must be (%d,), got %s" % (S + 1, tuple(g_loss.shape)))
+    if not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != (S, B, 3) or not stats.is_contiguous():
+        raise TypeError("stats must be a contiguous float64 array (%d,%d,3)" % (S, B))
+    _one_device(dev, [g_loss, stats])
+    if out is None:
+        g_disps = _empty([(B, 1, h, w) for h, w in hw], dev)
+    else:
+        if not isinstance(out, (list, tuple)) or len(out) != S:
+            raise TypeError("out needs one entry per scale")
+        g_disps = list(out)
+        for s, (t, (h, w)) in enumerate(zip(g_disps, hw)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, 1, h, w) or not t.is_contiguous() \
+                    or t.device != dev:
+                raise TypeError("out[%d] must be a contiguous float32 array (B,1,h,w) = %s on %s" % (s, (B, 1, h, w), dev))
+        d.accumulate = 1
+    _point(d.g_disp, g_disps)
+    d.stats, d.g_loss = stats.data_ptr(), g_loss.data_ptr()
+    _launch(dev, lib.sfm_disp_smooth_bwd, C.byref(d))
+    return g_disps
 
 
 class FusedLoss:

@@ -43,7 +43,7 @@ from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
            "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error",
-           "min_reprojection", "min_reprojection_loss"]
+           "min_reprojection", "min_reprojection_loss", "disparity_smoothness"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -716,13 +716,87 @@ def min_reprojection(errs, *, valid=None, ident=None, weights=None, norm="kept")
     return out[0], out[1], list(out[2:])
 
 
+class _DispSmooth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, weights, normalize, edge, *arrays):
+        disps, tgts = list(arrays[:S]), list(arrays[S:])
+        loss, stats = ops.disp_smooth_fwd(disps, tgts, weights, normalize, edge)
+        ctx.save_for_backward(stats, *disps, *tgts)
+        ctx.cfg = (S, weights, normalize, edge)
+        ctx.set_materialize_grads(False)
+        return loss[S], loss[:S]
+
+    @staticmethod
+    def backward(ctx, g_total, g_scales):
+        S, weights, normalize, edge = ctx.cfg
+        if g_total is None and g_scales is None:
+            return (None,) * (4 + 2 * S)
+        stats, disps, tgts = ctx.saved_tensors[0], list(ctx.saved_tensors[1:1 + S]), list(ctx.saved_tensors[1 + S:])
+        g_disps = ops.disp_smooth_bwd(disps, tgts, stats, _g_loss(S, g_total, g_scales, stats.device), weights, normalize, edge)
+        return (None,) * 4 + tuple(g_disps) + (None,) * S
+
+
+def disparity_smoothness(pred_disps, tgt, *, normalize=True, edge="mean_abs", weights=None):
+    """The second term of a Monodepth2-style loss: the edge-aware first-order smoothness of the disparity, every scale in two
+    launches (ops.disp_smooth_fwd) and one backward (ops.disp_smooth_bwd) -- per scale
+        d = disp / (disp.mean((2, 3), keepdim=True) + 1e-7)                                       (with `normalize`)
+        mean(|d[..., :, 1:] - d[..., :, :-1]| * exp(-a_x)) + mean(|d[..., 1:, :] - d[..., :-1, :]| * exp(-a_y))
+    with a = mean_c |dI_c| for edge "mean_abs" (Monodepth2's get_smooth_loss) or |mean_c dI_c| for "abs_mean" (compute_disp_smooth
+    of models/base_model.py:144-155; with normalize=False that function exactly).
+
+    pred_disps: a list of S tensors (B,1,h_s,w_s), float32, bfloat16 or float16 on a ROCm device (computed in float32, each
+      gradient returned in its input's dtype); h_s, w_s >= 3;
+    tgt: the frames whose edges relax the penalty, (B,3,H,W) float32 -- turned into the planar pyramid of `sfm_learner_loss`
+      (ops.pyramid), and then h_s, w_s must be H >> s, W >> s -- or a list of S per-scale tensors (B,3,h_s,w_s).  A constant: no
+      gradient flows to it;
+    weights: one per scale, default 2**-s.
+
+    Returns (total, per_scale): total, 0-d, = sum_s weights[s] * per_scale[s]; per_scale (S,).  Both are differentiable with respect
+    to `pred_disps` ONLY, the path through each sample's mean included; if none of them requires a gradient, nothing is recorded.
+    The mean is factored out of the sums (|D(d/M)| = |Dd| / |M|), which run in fp64 in a fixed order: the same bits on every call.
+    Nothing reads a device value on the host: it runs under torch.cuda.graph capture."""
+    if not isinstance(pred_disps, (list, tuple)):
+        raise TypeError("pred_disps must be a list of (B,1,h,w) tensors, one per scale")
+    S = len(pred_disps)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("1..%d scales, got %d" % (_lib.SFM_MAX_SCALES, S))
+    _lib.disp_smooth_edge_id(edge)
+    xs = []
+    for s, t in enumerate(pred_disps):
+        t = _dev_float(t, "pred_disps[%d]" % s, 4)
+        if t.shape[1] != 1 or t.shape[0] != (xs[0].shape[0] if xs else t.shape[0]):
+            raise TypeError("pred_disps[%d] must be (B,1,h,w) with the B of pred_disps[0], got %s" % (s, tuple(t.shape)))
+        xs.append(t)
+    B = xs[0].shape[0]
+    if isinstance(tgt, (list, tuple)):
+        if len(tgt) != S:
+            raise TypeError("pred_disps has %d scales but tgt has %d" % (S, len(tgt)))
+        tgts = ops._devs(tgt, "tgt", 4)
+    else:
+        tgt = ops._dev(tgt, "tgt", 4)
+        H, W = tgt.shape[2:]
+        for s, t in enumerate(xs):
+            if tuple(t.shape[2:]) != (H >> s, W >> s):
+                raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s for a tgt of %s, got %s"
+                                % (s, s, s, (B, 1, H >> s, W >> s), tuple(tgt.shape), tuple(t.shape)))
+        if tuple(tgt.shape[:2]) != (B, 3):
+            raise TypeError("tgt must be (B,3,H,W) = (%d,3,H,W), got %s" % (B, tuple(tgt.shape)))
+        tgts = ops.pyramid(tgt.detach(), S)
+    for s, (x, y) in enumerate(zip(xs, tgts)):
+        if tuple(y.shape) != (B, 3) + tuple(x.shape[2:]):
+            raise TypeError("tgt[%d] must be (B,3,h,w) = %s, got %s" % (s, (B, 3) + tuple(x.shape[2:]), tuple(y.shape)))
+        if x.device != xs[0].device or y.device != xs[0].device:
+            raise TypeError("every array must live on %s" % (xs[0].device,))
+    return _DispSmooth.apply(S, _scale_weights(weights, S), bool(normalize), edge, *xs, *[y.detach() for y in tgts])
+
+
 class _MinReprojLoss(torch.autograd.Function):
     """warp_pyramid -> photometric_error -> min_reprojection as ONE node: the six launches of the forward and the four of the
     backward run back to back from one `apply`, and autograd's engine visits one node with S + n_src leaves behind it."""
 
     @staticmethod
     def forward(ctx, tgt, src, K, cfg, S, *arrays):
-        ssim_rate, auto_mask, weights, norm = cfg
+        ssim_rate, auto_mask, weights, norm, smooth = cfg
         disps, poses = list(arrays[:S]), list(arrays[S:])
         B, n_src = src.shape[0], len(poses)
         pyr = ops.pyramid_hwc(src, S)
@@ -733,27 +807,35 @@ class _MinReprojLoss(torch.autograd.Function):
         if auto_mask:     # the identity reprojection: the planar source pyramid is (B,n_src,3,h,w) byte for byte
             idents = ops.photo_error_fwd([p.view(B, n_src, 3, p.shape[2], p.shape[3]) for p in ops.pyramid(src, S)], tgts, ssim_rate)
         loss, count, winners = ops.min_reproj_fwd(errs, valid, idents, weights, norm)
-        ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners)
-        ctx.cfg = (S, n_src, ssim_rate, weights, norm)
-        return loss[S]
+        if smooth is None:
+            ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners)
+            ctx.cfg = (S, n_src, ssim_rate, weights, norm, None)
+            return loss[S]
+        sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)      # on the target pyramid this node holds anyway
+        ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners, stats)
+        ctx.cfg = (S, n_src, ssim_rate, weights, norm, smooth)
+        return loss[S] + sm_loss[S]
 
     @staticmethod
     def backward(ctx, g_total):
-        S, n_src, ssim_rate, weights, norm = ctx.cfg
+        S, n_src, ssim_rate, weights, norm, smooth = ctx.cfg
         if g_total is None:
             return (None,) * (5 + S + n_src)
         K, count, rest = ctx.saved_tensors[0], ctx.saved_tensors[1], list(ctx.saved_tensors[2:])
         pyr, disps, poses = rest[:S], rest[S:2 * S], rest[2 * S:2 * S + n_src]
         rest = rest[2 * S + n_src:]
-        warped, tgts, winners = rest[:S], rest[S:2 * S], rest[2 * S:]
-        g_errs = ops.min_reproj_bwd(winners, count, _g_loss(S, g_total, None, count.device), n_src, weights, norm,
-                                    [tuple(t.shape[2:]) for t in disps])
+        warped, tgts, winners = rest[:S], rest[S:2 * S], rest[2 * S:3 * S]
+        g_loss = _g_loss(S, g_total, None, count.device)
+        g_errs = ops.min_reproj_bwd(winners, count, g_loss, n_src, weights, norm, [tuple(t.shape[2:]) for t in disps])
         d_warped = ops.photo_error_bwd(warped, tgts, ssim_rate, g_errs)
         d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", d_warped)
+        if smooth is not None:      # the smoothness gradient is added in place by its kernel: no aten call
+            ops.disp_smooth_bwd(disps, tgts, rest[3 * S], g_loss, *smooth, out=d_disps)
         return (None,) * 5 + tuple(d_disps) + tuple(d_poses)
 
 
-def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, *, ssim_rate, auto_mask=True, weights=None, norm="kept"):
+def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, *, ssim_rate, auto_mask=True, weights=None, norm="kept",
+                          smooth_weight=0.0, smooth_normalize=True, smooth_edge="mean_abs"):
     """The Monodepth2-style loss of INTEGRATION.md ("Your own loss on the library's warp") in one call and ONE autograd node: per
     pixel the smallest ssim_rate * SSIM + (1 - ssim_rate) * L1 error over the warped sources that are in view, averaged per scale
     over the pixels where it is strictly below the error of every UNWARPED source (`auto_mask`; off: over the pixels some source
@@ -767,14 +849,27 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
     Returns total (0-d).  Forward: the source pyramid, `warp_pyramid`'s launch with its valid masks, the target pyramid,
     `photometric_error`'s launch on the warped pyramid and, with `auto_mask`, on the unwarped one, `min_reprojection`'s two.  Backward:
     one launch each of min_reprojection, photometric_error and the warp, plus the warp's small fold.  The values are those of the three
-    stages called one after the other, bit for bit; nothing reads a device value on the host, so the step can be captured in a graph."""
+    stages called one after the other, bit for bit; nothing reads a device value on the host, so the step can be captured in a graph.
+
+    smooth_weight > 0 adds the second term of that objective in the SAME node: smooth_weight * the total of `disparity_smoothness`
+    on the target pyramid the node already holds, with `smooth_normalize` and `smooth_edge` as its `normalize` and `edge` and the
+    per-scale weights float32(smooth_weight * weights[s]).  Two more launches forward and one aten add of the two totals; one more
+    launch backward, which adds its gradient into d_disp in place.  The total and the gradients are those of the two calls added in
+    float32, bit for bit.  With smooth_weight == 0 (the default) nothing of this runs and `smooth_normalize` and `smooth_edge` are not looked at."""
+    if smooth_weight:       # (0, the default: nothing below is looked at, the call costs what it cost before the term existed)
+        smooth_weight = float(smooth_weight)
+        if not smooth_weight >= 0.0:
+            raise ValueError("smooth_weight must be >= 0, got %r" % (smooth_weight,))
+        _lib.disp_smooth_edge_id(smooth_edge)
     tgt = ops._dev(tgt_img, "tgt_img", 4)
     src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt)
     if K.requires_grad:
         raise TypeError("min_reprojection_loss does not differentiate the intrinsics: detach them")
     B, n_src, _, H, W = src.shape
     S = len(disps)
-    cfg = (float(ssim_rate), bool(auto_mask), _scale_weights(weights, S), norm)
+    weights = _scale_weights(weights, S)
+    smooth = (tuple(smooth_weight * w for w in weights), bool(smooth_normalize), smooth_edge) if smooth_weight else None
+    cfg = (float(ssim_rate), bool(auto_mask), weights, norm, smooth)
     _lib.min_reproj_norm_id(norm)
     return _MinReprojLoss.apply(tgt.detach(), src.detach().view(B, 3 * n_src, H, W), K, cfg, S, *disps, *poses)
 
