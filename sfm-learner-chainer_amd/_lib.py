@@ -127,6 +127,18 @@ class SfmDispSmoothDesc(C.Structure):     # include/sfmwarp_disp_smooth.h
     ]
 
 
+class SfmWarpFullResDesc(C.Structure):    # include/sfmwarp_full_res.h
+    _fields_ = [
+        ("B", C.c_int32), ("n_src", C.c_int32), ("n_scales", C.c_int32),
+        ("H", C.c_int32), ("W", C.c_int32),
+        ("h", C.c_int32 * SFM_MAX_SCALES), ("w", C.c_int32 * SFM_MAX_SCALES),
+        ("image_layout", C.c_int32),
+        ("src", _FP), ("disp", _FP * SFM_MAX_SCALES), ("intrinsics", _FP), ("pose", _FP * SFM_MAX_SRC),
+        ("warped", _FP * SFM_MAX_SCALES), ("valid", _FP * SFM_MAX_SCALES),
+        ("g_warped", _FP * SFM_MAX_SCALES), ("d_disp", _FP * SFM_MAX_SCALES), ("d_pose", _FP * SFM_MAX_SRC),
+    ]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -195,6 +207,14 @@ SMOOTH_SYMBOLS = {
 }
 
 
+# every symbol declared in the side header include/sfmwarp_full_res.h (to be folded into SYMBOLS together with that header)
+FULL_RES_SYMBOLS = {
+    "sfm_warp_full_res_fwd": (_I, [C.POINTER(SfmWarpFullResDesc), _V]),
+    "sfm_warp_full_res_bwd_workspace_bytes": (_Z, [C.POINTER(SfmWarpFullResDesc)]),
+    "sfm_warp_full_res_bwd": (_I, [C.POINTER(SfmWarpFullResDesc), _V, _Z, _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -205,7 +225,8 @@ def _load():
             "libsfmwarp.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SMOOTH_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SMOOTH_SYMBOLS.items()) \
+            + list(FULL_RES_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

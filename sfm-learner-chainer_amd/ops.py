@@ -9,12 +9,12 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpPyramidDesc, check, lib
+from ._lib import SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpFullResDesc, SfmWarpPyramidDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
            "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "min_reproj_fwd", "min_reproj_bwd",
-           "disp_smooth_fwd", "disp_smooth_bwd"]
+           "disp_smooth_fwd", "disp_smooth_bwd", "warp_full_res_fwd", "warp_full_res_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -518,6 +518,82 @@ def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped):
         raise ValueError(_lib.last_error() or "invalid warp pyramid descriptor")
     ws, ptr, have = _place_workspace(None, nbytes, dev)
     _launch(dev, lib.sfm_warp_pyramid_bwd, C.byref(d), C.c_void_p(ptr), have)
+    return d_disps, d_poses
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the full-resolution multi-scale warp: every disparity upsampled inside the warp (include/sfmwarp_full_res.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _warp_full_res_desc(src, disps, poses, K, layout):
+    """(descriptor with the inputs bound, the arrays it points at, B, n_src, (H, W), [(h, w)], device) for warp_full_res_fwd / _bwd"""
+    if layout not in _LAYOUTS:
+        raise ValueError("layout must be 'planar' or 'hwc', got %r" % (layout,))
+    hwc = layout == "hwc"
+    S, n_src = len(disps), len(poses)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES or not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("disps needs one entry per scale (1..%d), poses one per source (1..%d)" % (_lib.SFM_MAX_SCALES, _lib.SFM_MAX_SRC))
+    src, disps, poses = _dev(src, "src", 5 if hwc else 4), _devs(disps, "disps", 4), _devs(poses, "poses", 2)
+    K = _dev(K, "intrinsics", 3)
+    B, dev = src.shape[0], src.device
+    H, W = (src.shape[2:4] if hwc else src.shape[2:])
+    if tuple(src.shape) != ((B, n_src, H, W, 3) if hwc else (B, 3 * n_src, H, W)):
+        raise TypeError("src must be %s for %d poses, got %s" % ("(B,n_src,H,W,3)" if hwc else "(B,3*n_src,H,W)", n_src, tuple(src.shape)))
+    if tuple(K.shape) != (B, 3, 3):
+        raise TypeError("intrinsics must be (B,3,3), got %s" % (tuple(K.shape),))
+    for s, t in enumerate(disps):
+        if tuple(t.shape[:2]) != (B, 1):
+            raise TypeError("disps[%d] must be (B,1,h,w) = (%d,1,h,w), got %s" % (s, B, tuple(t.shape)))
+    for i, t in enumerate(poses):
+        if tuple(t.shape) != (B, 6):
+            raise TypeError("poses[%d] must be (B,6)" % i)
+    _one_device(dev, disps + poses + [K])
+    hw = [tuple(t.shape[2:]) for t in disps]
+    d = SfmWarpFullResDesc()
+    d.B, d.n_src, d.n_scales, d.H, d.W, d.image_layout = B, n_src, S, H, W, _LAYOUTS[layout]
+    for s, (h, w) in enumerate(hw):
+        d.h[s], d.w[s] = h, w
+    d.src, d.intrinsics = src.data_ptr(), K.data_ptr()
+    for field, arrays in ((d.disp, disps), (d.pose, poses)):
+        _point(field, arrays)
+    return d, (src, disps, poses, K), B, n_src, (H, W), hw, dev
+
+
+def warp_full_res_fwd(src, disps, poses, K, layout, want_valid=False):
+    """ONE full-resolution source set warped with the disparity of every scale, each upsampled to (H, W) inside the kernel, in ONE
+    launch (sfm_warp_full_res_fwd): src (B,3*n_src,H,W) for layout "planar" or (B,n_src,H,W,3) for "hwc", disps[s] (B,1,h_s,w_s) of any
+    sizes, poses[i] (B,6), K (B,3,3) -> [warped_s (B,n_src,3,H,W)]: `warp_pyramid_fwd` at equal sizes on `resize` of each disparity
+    (itself where it has the full size), bit for bit; with `want_valid` also [valid_s (B,n_src,H,W)]."""
+    d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout)
+    warped = _empty([(B, n_src, 3, H, W)] * len(hw), dev)
+    valid = _empty([(B, n_src, H, W)] * len(hw), dev) if want_valid else None
+    _point(d.warped, warped)
+    _point(d.valid, valid or ())
+    _launch(dev, lib.sfm_warp_full_res_fwd, C.byref(d))
+    return (warped, valid) if want_valid else warped
+
+
+def warp_full_res_bwd(src, disps, poses, K, layout, g_warped, ws=None):
+    """The backward of `warp_full_res_fwd` for the upstream gradients g_warped[s] (B,n_src,3,H,W): one launch over the pixels, one
+    that gathers every low-resolution gradient and a small fold (sfm_warp_full_res_bwd) -> ([d_disp_s (B,1,h_s,w_s)], [d_pose_i
+    (B,6)]): `warp_pyramid_bwd` at equal sizes followed by `resize_bwd` of each d_disp, bit for bit.  No atomics: the same bits on
+    every call, whatever `ws` (the caller's workspace, or None for a fresh one) held."""
+    d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout)
+    if len(g_warped) != len(hw):
+        raise TypeError("g_warped needs one entry per scale")
+    g_warped = _devs(g_warped, "g_warped", 5)
+    for s, g in enumerate(g_warped):
+        if tuple(g.shape) != (B, n_src, 3, H, W) or g.device != dev:
+            raise TypeError("g_warped[%d] must be (B,n_src,3,H,W) = %s on %s" % (s, (B, n_src, 3, H, W), dev))
+    d_disps = _empty([(B, 1, h, w) for h, w in hw], dev)
+    d_poses = _empty([(B, 6)] * n_src, dev)
+    for field, arrays in ((d.g_warped, g_warped), (d.d_disp, d_disps), (d.d_pose, d_poses)):
+        _point(field, arrays)
+    nbytes = lib.sfm_warp_full_res_bwd_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        check(lib.sfm_warp_full_res_bwd(C.byref(d), None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid full-resolution warp descriptor")
+    ws, ptr, have = _place_workspace(ws, nbytes, dev)
+    _launch(dev, lib.sfm_warp_full_res_bwd, C.byref(d), C.c_void_p(ptr), have)
     return d_disps, d_poses
 
 

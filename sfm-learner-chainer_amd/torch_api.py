@@ -7,6 +7,8 @@ grad_fn.  This module hands those outputs to libsfmwarp and the gradients it com
   projective_inverse_warp             models/transform.py:156-193 (ops.warp_fwd / ops.warp_bwd / ops.warp_bwd_intrinsics)
   warp_pyramid                        the warped source images of EVERY (scale, source) of a step, models/base_model.py:69-94, for a
                                       loss of the caller's own (ops.pyramid_hwc, ops.warp_pyramid_fwd / ops.warp_pyramid_bwd)
+  warp_full_res                       the full-resolution sources warped with the disparity of EVERY scale, each upsampled inside the
+                                      warp: Monodepth2's full-resolution multi-scale (ops.warp_full_res_fwd / ops.warp_full_res_bwd)
   photometric_error                   alpha * SSIM + (1 - alpha) * L1 per pixel (models/base_model.py:96,126-142) of every (scale, image) of
                                       a step, differentiable w.r.t. the images (ops.photo_error_fwd / ops.photo_error_bwd)
   min_reprojection                    the stage behind it: per pixel the minimum over the sources, the auto-mask against the unwarped
@@ -43,7 +45,7 @@ from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
            "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error",
-           "min_reprojection", "min_reprojection_loss", "disparity_smoothness"]
+           "min_reprojection", "min_reprojection_loss", "disparity_smoothness", "warp_full_res"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -566,6 +568,90 @@ def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=F
     return (list(out[:S]), list(out[S:])) if return_valid else list(out)
 
 
+class _WarpFullRes(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, K, S, want_valid, *arrays):
+        disps, poses = list(arrays[:S]), list(arrays[S:])
+        hwc = ops.pyramid_hwc(src, 1)[0]
+        out = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", want_valid)
+        warped, valid = out if want_valid else (out, [])
+        ctx.save_for_backward(K, hwc, *disps, *poses)
+        ctx.S = S
+        ctx.mark_non_differentiable(*valid)
+        ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
+        return tuple(warped) + tuple(valid)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        S = ctx.S
+        K, hwc, saved = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:]
+        disps, poses = list(saved[:S]), list(saved[S:])
+        B, n_src, H, W = hwc.shape[:4]
+        g = [torch.zeros((B, n_src, 3, H, W), dtype=torch.float32, device=hwc.device) if gr is None
+             else gr.to(torch.float32).contiguous() for gr in grads[:S]]
+        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", g)
+        return (None, None, None, None) + tuple(d_disps) + tuple(d_poses)
+
+
+def _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, who):
+    """The inputs of `warp_full_res`, checked: src_imgs (B,n_src,3,H,W), 1..8 sources, 1..8 scales, intrinsics (B,3,3) or (B,S,3,3)
+    -- of which [:, 0], the full-resolution camera, is used --, a constant, pred_disps[s] (B,1,h_s,w_s) of any size, the poses, and
+    last that every array lives on the frames' device.  -> (src, K (B,3,3), disps, poses)"""
+    src = ops._dev(src_imgs, "src_imgs", 5)
+    B, n_src, c, H, W = src.shape
+    if c != 3:
+        raise TypeError("src_imgs must be (B,n_src,3,H,W), got %s" % (tuple(src.shape),))
+    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d source images, got %d" % (_lib.SFM_MAX_SRC, n_src))
+    if not isinstance(pred_disps, (list, tuple)) or not 1 <= len(pred_disps) <= _lib.SFM_MAX_SCALES:
+        raise TypeError("pred_disps: a list of 1..%d tensors (B,1,h,w)" % _lib.SFM_MAX_SCALES)
+    S = len(pred_disps)
+    K = ops._dev(intrinsics, "intrinsics")
+    if K.requires_grad:
+        raise TypeError("%s does not differentiate the intrinsics: detach them, or warp per (scale, source) with "
+                        "projective_inverse_warp, which returns their gradient" % who)
+    if tuple(K.shape) == (B, S, 3, 3):
+        K = K[:, 0].contiguous()
+    elif tuple(K.shape) != (B, 3, 3):
+        raise TypeError("intrinsics must be (B,3,3) or (B,%d,3,3), got %s" % (S, tuple(K.shape)))
+    disps = []
+    for s, t in enumerate(pred_disps):
+        t = _dev_float(t, "pred_disps[%d]" % s, 4)
+        if tuple(t.shape[:2]) != (B, 1):
+            raise TypeError("pred_disps[%d] must be (B,1,h,w) = (%d,1,h,w), got %s" % (s, B, tuple(t.shape)))
+        disps.append(t)
+    poses = _poses(pred_poses, B, n_src)
+    for t in [K] + disps + poses:
+        if t.device != src.device:
+            raise TypeError("every array must live on %s, one is on %s" % (src.device, t.device))
+    return src, K, disps, poses
+
+
+def warp_full_res(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False):
+    """Monodepth2's "full-resolution multi-scale" warp: the disparity of every scale upsampled to the input resolution and the
+    FULL-RESOLUTION sources warped with it through the full-resolution camera -- what `resize_images` per scale followed by
+    `projective_inverse_warp` per (scale, source) computes, in one launch and without a full-resolution copy of any disparity.
+
+    src_imgs (B,n_src,3,H,W) float32: constants -- no gradient flows to them;
+    intrinsics (B,3,3) float32, the full-resolution camera, or the (B,S,3,3) `sfm_learner_loss` takes, of which [:, 0] is used: a
+      constant -- if it requires grad this raises TypeError;
+    pred_disps: S tensors (B,1,h_s,w_s) of ANY sizes (a scale of size (H, W) is used as it is, every other one is resampled as
+      `resize_images` does: align-corners bilinear, the reference's F.resize_images); pred_poses: n_src tensors (B,6) or one packed
+      (B,6*n_src) tensor; float32, bfloat16 or float16 on a ROCm device, computed in float32, each gradient returned in its input's dtype.
+
+    Returns a list of S tensors (B,n_src,3,H,W): [s][:, i] is projective_inverse_warp of source i with depth 1 / resize_images(
+    pred_disps[s], (H, W)), bit for bit.  With `return_valid` also the list of S masks (B,n_src,H,W), as `warp_pyramid` returns them.
+
+    Two launches forward (the pixel-interleaved copy of the sources, the warp of all scales and sources); backward one launch over
+    the pixels, one that gathers the gradient of every low-resolution disparity and a small fold, whatever S and n_src are.  No
+    atomics: the same bits on every call.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture."""
+    src, K, disps, poses = _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, "warp_full_res")
+    B, n_src, _, H, W = src.shape
+    S = len(disps)
+    out = _WarpFullRes.apply(src.detach().view(B, 3 * n_src, H, W), K, S, bool(return_valid), *disps, *poses)
+    return (list(out[:S]), list(out[S:])) if return_valid else list(out)
+
+
 class _PhotoError(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ssim_rate, S, *arrays):
@@ -834,8 +920,54 @@ class _MinReprojLoss(torch.autograd.Function):
         return (None,) * 5 + tuple(d_disps) + tuple(d_poses)
 
 
+class _MinReprojLossFullRes(torch.autograd.Function):
+    """warp_full_res -> photometric_error -> min_reprojection as ONE node, every scale compared with the full-resolution target; the
+    smoothness term stays where _MinReprojLoss has it: each disparity at its own size on the target pyramid."""
+
+    @staticmethod
+    def forward(ctx, tgt, src, K, cfg, S, *arrays):
+        ssim_rate, auto_mask, weights, norm, smooth = cfg
+        disps, poses = list(arrays[:S]), list(arrays[S:])
+        B, n_src = src.shape[0], len(poses)
+        H, W = tgt.shape[2:]
+        hwc = ops.pyramid_hwc(src, 1)[0]
+        warped, valid = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", True)
+        errs = ops.photo_error_fwd(warped, [tgt] * S, ssim_rate)
+        idents = None
+        if auto_mask:     # the identity reprojection, ONCE: the target and the unwarped sources are the same at every scale
+            idents = ops.photo_error_fwd([src.view(B, n_src, 3, H, W)], [tgt], ssim_rate) * S
+        loss, count, winners = ops.min_reproj_fwd(errs, valid, idents, weights, norm)
+        if smooth is None:
+            ctx.save_for_backward(K, count, hwc, tgt, *disps, *poses, *warped, *winners)
+            ctx.cfg = (S, n_src, ssim_rate, weights, norm, None)
+            return loss[S]
+        tgts = ops.pyramid(tgt, S)
+        sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)
+        ctx.save_for_backward(K, count, hwc, tgt, *disps, *poses, *warped, *winners, stats, *tgts[1:])
+        ctx.cfg = (S, n_src, ssim_rate, weights, norm, smooth)
+        return loss[S] + sm_loss[S]
+
+    @staticmethod
+    def backward(ctx, g_total):
+        S, n_src, ssim_rate, weights, norm, smooth = ctx.cfg
+        if g_total is None:
+            return (None,) * (5 + S + n_src)
+        K, count, hwc, tgt = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        disps, poses = rest[:S], rest[S:S + n_src]
+        rest = rest[S + n_src:]
+        warped, winners = rest[:S], rest[S:2 * S]
+        g_loss = _g_loss(S, g_total, None, count.device)
+        g_errs = ops.min_reproj_bwd(winners, count, g_loss, n_src, weights, norm, [tuple(tgt.shape[2:])] * S)
+        d_warped = ops.photo_error_bwd(warped, [tgt] * S, ssim_rate, g_errs)
+        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", d_warped)
+        if smooth is not None:      # the smoothness gradient is added in place by its kernel: no aten call
+            ops.disp_smooth_bwd(disps, [tgt] + rest[2 * S + 1:], rest[2 * S], g_loss, *smooth, out=d_disps)
+        return (None,) * 5 + tuple(d_disps) + tuple(d_poses)
+
+
 def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, *, ssim_rate, auto_mask=True, weights=None, norm="kept",
-                          smooth_weight=0.0, smooth_normalize=True, smooth_edge="mean_abs"):
+                          smooth_weight=0.0, smooth_normalize=True, smooth_edge="mean_abs", full_res=False):
     """The Monodepth2-style loss of INTEGRATION.md ("Your own loss on the library's warp") in one call and ONE autograd node: per
     pixel the smallest ssim_rate * SSIM + (1 - ssim_rate) * L1 error over the warped sources that are in view, averaged per scale
     over the pixels where it is strictly below the error of every UNWARPED source (`auto_mask`; off: over the pixels some source
@@ -855,23 +987,42 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
     on the target pyramid the node already holds, with `smooth_normalize` and `smooth_edge` as its `normalize` and `edge` and the
     per-scale weights float32(smooth_weight * weights[s]).  Two more launches forward and one aten add of the two totals; one more
     launch backward, which adds its gradient into d_disp in place.  The total and the gradients are those of the two calls added in
-    float32, bit for bit.  With smooth_weight == 0 (the default) nothing of this runs and `smooth_normalize` and `smooth_edge` are not looked at."""
+    float32, bit for bit.  With smooth_weight == 0 (the default) nothing of this runs and `smooth_normalize` and `smooth_edge` are not looked at.
+
+    full_res=True is Monodepth2's full-resolution multi-scale form, still ONE node: `warp_full_res` instead of `warp_pyramid` (every
+    disparity upsampled inside the warp of the full-resolution sources; intrinsics may then also be the full-resolution (B,3,3)
+    alone, and pred_disps[s] may have any size unless smooth_weight > 0), `photometric_error` of the S full-resolution warped sets
+    against the full-resolution target, the identity error computed once and handed to `min_reprojection` for every scale, and the
+    smoothness term unchanged: each disparity at its own size on the target pyramid.  The total and the gradients are those of
+    these stages called one after the other, bit for bit.  With full_res=False (the default) the call is what it was."""
     if smooth_weight:       # (0, the default: nothing below is looked at, the call costs what it cost before the term existed)
         smooth_weight = float(smooth_weight)
         if not smooth_weight >= 0.0:
             raise ValueError("smooth_weight must be >= 0, got %r" % (smooth_weight,))
         _lib.disp_smooth_edge_id(smooth_edge)
     tgt = ops._dev(tgt_img, "tgt_img", 4)
-    src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt)
-    if K.requires_grad:
-        raise TypeError("min_reprojection_loss does not differentiate the intrinsics: detach them")
-    B, n_src, _, H, W = src.shape
+    if full_res:
+        src, K, disps, poses = _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, "min_reprojection_loss")
+        B, n_src, _, H, W = src.shape
+        if tuple(tgt.shape) != (B, 3, H, W) or tgt.device != src.device:
+            raise TypeError("tgt_img must be (B,3,H,W) = %s on %s, got %s on %s" % ((B, 3, H, W), src.device, tuple(tgt.shape), tgt.device))
+        for s, t in enumerate(disps):       # (the smoothness term reads the target pyramid at each disparity's own size)
+            if smooth_weight and tuple(t.shape[2:]) != (H >> s, W >> s):
+                raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s with smooth_weight > 0, got %s"
+                                % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
+        node = _MinReprojLossFullRes
+    else:
+        src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt)
+        if K.requires_grad:
+            raise TypeError("min_reprojection_loss does not differentiate the intrinsics: detach them")
+        B, n_src, _, H, W = src.shape
+        node = _MinReprojLoss
     S = len(disps)
     weights = _scale_weights(weights, S)
     smooth = (tuple(smooth_weight * w for w in weights), bool(smooth_normalize), smooth_edge) if smooth_weight else None
     cfg = (float(ssim_rate), bool(auto_mask), weights, norm, smooth)
     _lib.min_reproj_norm_id(norm)
-    return _MinReprojLoss.apply(tgt.detach(), src.detach().view(B, 3 * n_src, H, W), K, cfg, S, *disps, *poses)
+    return node.apply(tgt.detach(), src.detach().view(B, 3 * n_src, H, W), K, cfg, S, *disps, *poses)
 
 
 def multi_scale_intrinsics(K, n_scales):
