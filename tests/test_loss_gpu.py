@@ -6,6 +6,7 @@ Tolerances (fp32, north_star: 1e-4 relative on the loss):
   * d_disp / d_pose / d_mask / d_src ...... 2e-3 of the array's largest magnitude, element-wise,
     outside knife-edge pixels (see tests/util.py); they are sums of many fp32 terms whose
     order differs between the oracle (NumPy) and the wave-level reductions.
+(tests/test_loss_exact_gpu.py compares every element of the same gradients with the fp64 oracle, without a mask, on inputs that have no knife-edge pixel.)
 """
 import os
 
