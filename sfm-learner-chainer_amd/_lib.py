@@ -139,6 +139,23 @@ class SfmWarpFullResDesc(C.Structure):    # include/sfmwarp_full_res.h
     ]
 
 
+# include/sfmwarp_conventions.h: the padding of the SSIM window and the upsampling of the full-resolution warp's disparities
+SSIM_PAD_ZERO, SSIM_PAD_REFLECT = 0, 1
+SSIM_PADDINGS = {"zero": SSIM_PAD_ZERO, "reflect": SSIM_PAD_REFLECT}
+UPSAMPLE_ALIGN_CORNERS, UPSAMPLE_HALF_PIXEL = 0, 1
+UPSAMPLES = {"align_corners": UPSAMPLE_ALIGN_CORNERS, "half_pixel": UPSAMPLE_HALF_PIXEL}
+
+
+def ssim_padding_id(name, what="padding"):
+    """SFM_SSIM_PAD_* of a `padding` argument; anything outside the table is a ValueError"""
+    return _setting(SSIM_PADDINGS, what, name)
+
+
+def upsample_id(name):
+    """SFM_UPSAMPLE_* of an `upsample` argument; anything outside the table is a ValueError"""
+    return _setting(UPSAMPLES, "upsample", name)
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -215,6 +232,16 @@ FULL_RES_SYMBOLS = {
 }
 
 
+# every symbol declared in the side header include/sfmwarp_conventions.h (to be folded into SYMBOLS together with that header)
+CONV_SYMBOLS = {
+    "sfm_photo_error_pad_fwd": (_I, [C.POINTER(SfmPhotoErrorDesc), C.c_int32, _V]),
+    "sfm_photo_error_pad_bwd": (_I, [C.POINTER(SfmPhotoErrorDesc), C.c_int32, _V]),
+    "sfm_warp_full_res_up_fwd": (_I, [C.POINTER(SfmWarpFullResDesc), C.c_int32, _V]),
+    "sfm_warp_full_res_up_bwd_workspace_bytes": (_Z, [C.POINTER(SfmWarpFullResDesc), C.c_int32]),
+    "sfm_warp_full_res_up_bwd": (_I, [C.POINTER(SfmWarpFullResDesc), C.c_int32, _V, _Z, _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -226,7 +253,7 @@ def _load():
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SMOOTH_SYMBOLS.items()) \
-            + list(FULL_RES_SYMBOLS.items()):
+            + list(FULL_RES_SYMBOLS.items()) + list(CONV_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -10,13 +10,16 @@
 // The forward pools once: 62 useful columns per strip, rows y0-1 .. y1.  The backward pools twice -- the statistics at p, then the
 // three partial maps at q -- hence 60 useful columns and rows y0-2 .. y1+1; the statistics are recomputed, never stored.
 // Outside the image every load is clamped to an address inside it and its value replaced by zero: the zero padding of
-// F.average_pooling_2d costs no divergent load.
+// F.average_pooling_2d costs no divergent load.  REFLECT (include/sfmwarp_conventions.h) is a template parameter of both kernels: the
+// same march over the image extended by ReflectionPad2d(1) -- the ring's loads are clamps of the same kind, its share of the backward
+// is folded back in registers --, the zero-padded instantiations keep their code.
 //
 // The pooled quantities stay 3x3 SUMS (sx = 9 mu_x, ...): the SSIM index is a ratio in which every 1/9 cancels,
 //   S = (2 sx sy + 81 c1)(2 (9 sxy - sx sy) + 81 c2) / ((sx^2 + sy^2 + 81 c1)(9 sxx - sx^2 + 9 syy - sy^2 + 81 c2)),
 // one rounding per term less than dividing each sum first.
 #include "sfm_common.h"
 #include "sfm_warp_pixel.h"
+#include "../../include/sfmwarp_conventions.h"
 
 namespace sfm {
 
@@ -116,12 +119,21 @@ struct PeRow {
   float x[3], y[3];
 };
 
+// REFLECT (include/sfmwarp_conventions.h): the image extended by ReflectionPad2d(1).  Index -1 reads index 1 and index n reads index
+// n-2 (n >= 2); whatever lies further out is clamped into the image and dropped, as without reflection.
+__device__ __forceinline__ int pe_reflect(const int i, const int n) {
+  const int m = i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i);
+  return min(max(m, 0), n - 1);
+}
+
+template <bool REFLECT = false>
 __device__ __forceinline__ PeRow pe_load_row(const float* X, const float* Y, const int row, const int H, const int W, const unsigned xc,
                                              const bool colin) {
   PeRow o;
-  const bool in = colin & (row >= 0) & (row < H);
+  // (REFLECT: rows -1 and H count too, read from rows 1 and H-2 -- the row index stays uniform over the wave)
+  const bool in = REFLECT ? colin & (row >= -1) & (row <= H) : colin & (row >= 0) & (row < H);
   const size_t P = (size_t)H * W;
-  const size_t at = (size_t)min(max(row, 0), H - 1) * W;      // clamped: the load is in bounds, the value is dropped
+  const size_t at = (size_t)(REFLECT ? pe_reflect(row, H) : min(max(row, 0), H - 1)) * W;      // in bounds; a value outside is dropped
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float xv = ldf(X + c * P + at, xc), yv = ldf(Y + c * P + at, xc);
@@ -131,15 +143,17 @@ __device__ __forceinline__ PeRow pe_load_row(const float* X, const float* Y, con
   return o;
 }
 
-template <bool SSIM>
+template <bool SSIM, bool REFLECT = false>
 __global__ void __launch_bounds__(PE_BLOCK) photo_err_fwd_kernel(const PhotoErrArgs A) {
   const PhotoErrTile t = photo_err_tile<PE_FWD_STRIP>(A);
   if (!t.any) return;
   const int H = t.H, W = t.W, lane = threadIdx.x & 63;
   const size_t P = (size_t)H * W;
   const int x = t.x0 + lane - 1;
-  const bool colin = (x >= 0) & (x < W);
-  const unsigned xc = (unsigned)min(max(x, 0), W - 1);
+  // the lane's value counts: the image's columns, with REFLECT the ring columns -1 and W too, loaded from 1 and W-2 -- a per-lane
+  // clamp of the same kind, no divergent load (a lane that writes has xc == x either way)
+  const bool colin = REFLECT ? (x >= -1) & (x <= W) : (x >= 0) & (x < W);
+  const unsigned xc = (unsigned)(REFLECT ? pe_reflect(x, W) : min(max(x, 0), W - 1));
   const bool mine = (lane >= 1) & (lane <= PE_FWD_STRIP) & (x < W);      // the columns this lane writes
   const float* X = A.img[t.s] + t.image * 3 * P;
   const float* Y = A.tgt[t.s] + t.sample * 3 * P;
@@ -160,7 +174,7 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_fwd_kernel(const PhotoErrA
       prev.x[c] = prev.y[c] = 0.f;
     }
     for (int r = t.y0 - 1; r <= t.y1; ++r) {
-      const PeRow v = pe_load_row(X, Y, r, H, W, xc, colin);
+      const PeRow v = pe_load_row<REFLECT>(X, Y, r, H, W, xc, colin);
       float h[3][5];
 #pragma unroll
       for (int c = 0; c < 3; ++c) pe_hsums(v.x[c], v.y[c], h[c]);
@@ -186,7 +200,16 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_fwd_kernel(const PhotoErrA
   }
 }
 
-template <bool SSIM>
+// hsum3 of a partial map under REFLECT: the adjoint of "pad, then pool" along the row.  What the pooling sends to padded column -1
+// comes from column 0 alone and belongs to column 1, what it sends to column W from column W-1 alone and belongs to column W-2: the
+// neighbour's value hsum3 already holds, counted once more there (both at W == 3; columns 1 and 0 at W == 2).
+__device__ __forceinline__ float pe_hsum3_fold(float m, const bool again_left, const bool again_right) {
+  asm("" : "+v"(m));
+  const float l = from_left(m), r = from_right(m);
+  return ((m + l) + r) + ((again_left ? l : 0.f) + (again_right ? r : 0.f));
+}
+
+template <bool SSIM, bool REFLECT = false>
 __global__ void __launch_bounds__(PE_BLOCK) photo_err_bwd_kernel(const PhotoErrArgs A) {
   const PhotoErrTile t = photo_err_tile<PE_BWD_STRIP>(A);
   if (!t.any) return;
@@ -194,7 +217,10 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_bwd_kernel(const PhotoErrA
   const size_t P = (size_t)H * W;
   const int x = t.x0 + lane - 2;
   const bool colin = (x >= 0) & (x < W);
-  const unsigned xc = (unsigned)min(max(x, 0), W - 1);
+  // the lane's X and Y count: colin, with REFLECT the ring columns -1 and W too, loaded from 1 and W-2 (g_err and the maps stay on colin)
+  const bool colld = REFLECT ? (x >= -1) & (x <= W) : colin;
+  const unsigned xc = (unsigned)(REFLECT ? pe_reflect(x, W) : min(max(x, 0), W - 1));
+  const bool again_left = x == 1, again_right = x == W - 2;      // REFLECT: the columns that receive the ring's share
   const bool mine = (lane >= 2) & (lane < 2 + PE_BWD_STRIP) & (x < W);
   const float* X = A.img[t.s] + t.image * 3 * P;
   const float* Y = A.tgt[t.s] + t.sample * 3 * P;
@@ -223,12 +249,12 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_bwd_kernel(const PhotoErrA
     }
     const float kw = -0.5f * A.w_ssim;
     for (int r = t.y0 - 2; r <= t.y1 + 1; ++r) {
-      const PeRow v = pe_load_row(X, Y, r, H, W, xc, colin);
+      const PeRow v = pe_load_row<REFLECT>(X, Y, r, H, W, xc, colld);
       float h[3][5], hm[3][3];
 #pragma unroll
       for (int c = 0; c < 3; ++c) pe_hsums(v.x[c], v.y[c], h[c]);
       // the upstream gradient of row p = r-1, zero outside the image: so are the partial maps there (the second pooling is
-      // zero-padded like the first)
+      // zero-padded like the first; with REFLECT the maps exist at image pixels only and the ring's share is folded back below)
       const int p = r - 1;
       const bool pin = colin & (p >= 0) & (p < H);
       const float gl = ldf(G + (size_t)min(max(p, 0), H - 1) * W, xc);
@@ -245,9 +271,15 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_bwd_kernel(const PhotoErrA
           const float m0 = kr * (2.f * (st.sy * (st.n2 - st.n1) - st.S * st.sx * (st.d2 - st.d1)));
           const float m1 = kappa * (-st.S) * rcp_refined(st.d2);
           const float m2 = kr * st.n1;
-          hm[c][0] = hsum3(kappa != 0.f ? m0 : 0.f);
-          hm[c][1] = hsum3(kappa != 0.f ? m1 : 0.f);
-          hm[c][2] = hsum3(kappa != 0.f ? m2 : 0.f);
+          if constexpr (REFLECT) {
+            hm[c][0] = pe_hsum3_fold(kappa != 0.f ? m0 : 0.f, again_left, again_right);
+            hm[c][1] = pe_hsum3_fold(kappa != 0.f ? m1 : 0.f, again_left, again_right);
+            hm[c][2] = pe_hsum3_fold(kappa != 0.f ? m2 : 0.f, again_left, again_right);
+          } else {
+            hm[c][0] = hsum3(kappa != 0.f ? m0 : 0.f);
+            hm[c][1] = hsum3(kappa != 0.f ? m1 : 0.f);
+            hm[c][2] = hsum3(kappa != 0.f ? m2 : 0.f);
+          }
         }
       } else {
 #pragma unroll
@@ -256,11 +288,19 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_bwd_kernel(const PhotoErrA
       if (r >= t.y0 + 2) {       // the maps of rows r-3, r-2, r-1 are in hand: row q = r-2 goes out
         const size_t at = (size_t)(r - 2) * W;
         const float gq = A.w_l1 * g2;
+        // REFLECT, the same fold down the columns: padded row -1 holds the sums of row 0 alone and belongs to row 1, padded row H
+        // those of row H-1 alone and belongs to row H-2 -- the previous or the next row's sums once more (uniform over the wave)
+        const float up_again = (REFLECT && r - 2 == 1) ? 1.f : 0.f, down_again = (REFLECT && r - 2 == H - 2) ? 1.f : 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          const float sa = (ma[c][0] + mb[c][0]) + hm[c][0];
-          const float sb = (ma[c][1] + mb[c][1]) + hm[c][1];
-          const float se = (ma[c][2] + mb[c][2]) + hm[c][2];
+          float sa = (ma[c][0] + mb[c][0]) + hm[c][0];
+          float sb = (ma[c][1] + mb[c][1]) + hm[c][1];
+          float se = (ma[c][2] + mb[c][2]) + hm[c][2];
+          if constexpr (REFLECT) {      // the three summed maps are completed first
+            sa = sa + (up_again * ma[c][0] + down_again * hm[c][0]);
+            sb = sb + (up_again * ma[c][1] + down_again * hm[c][1]);
+            se = se + (up_again * ma[c][2] + down_again * hm[c][2]);
+          }
           const float d = gq * signf(p2.x[c] - p2.y[c]) + (sa + 18.f * (p2.x[c] * sb + p2.y[c] * se));
           if (mine) stf(out + c * P + at, xc, d);
         }
@@ -278,7 +318,8 @@ __global__ void __launch_bounds__(PE_BLOCK) photo_err_bwd_kernel(const PhotoErrA
 }
 
 // What both calls check and fill in, in the order the header states.  bwd: the pointers of the backward, else those of the forward.
-static int photo_err_setup(PhotoErrArgs& A, const char* who, const SfmPhotoErrorDesc* d, const bool bwd) {
+static int photo_err_setup(PhotoErrArgs& A, const char* who, const SfmPhotoErrorDesc* d, const bool bwd,
+                           const int32_t padding = SFM_SSIM_PAD_ZERO) {
   SFM_REQUIRE(d, SFM_ERR_NULL, "%s: NULL descriptor", who);
   const int strip = bwd ? PE_BWD_STRIP : PE_FWD_STRIP;
   const auto tiles = [&A, d, strip](const int s, const int H, const int W) {
@@ -286,14 +327,39 @@ static int photo_err_setup(PhotoErrArgs& A, const char* who, const SfmPhotoError
     A.nchunk[s] = (H + PE_ROWS - 1) / PE_ROWS;
     return (long long)d->n_img * A.nstrip[s] * A.nchunk[s];
   };
-  if (int e = check_pyramid_shape(who, d->B, d->n_img, "n_img", d->n_scales, d->H, d->W, "wavefront tiles", ": the grid would overflow",
-                                  tiles, A.H, A.W, A.begin))
-    return e;
+  if (padding != SFM_SSIM_PAD_REFLECT) {
+    if (int e = check_pyramid_shape(who, d->B, d->n_img, "n_img", d->n_scales, d->H, d->W, "wavefront tiles", ": the grid would overflow",
+                                    tiles, A.H, A.W, A.begin))
+      return e;
+  } else {
+    // The same checks in the same order with one difference: check_pyramid_shape refuses a frame below 3 x 3, which the zero-padded
+    // calls keep refusing; the reflected window needs two rows and columns and no more, so here the shape group asks only for a
+    // frame that exists and the reflection's own floor follows the settings, where include/sfmwarp_conventions.h states it.
+    SFM_REQUIRE(d->n_img >= 1 && d->n_img <= SFM_MAX_SRC, SFM_ERR_SHAPE, "%s: n_img=%d, need 1..%d", who, d->n_img, SFM_MAX_SRC);
+    SFM_REQUIRE(d->n_scales >= 1 && d->n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "%s: n_scales=%d, need 1..%d", who, d->n_scales,
+                SFM_MAX_SCALES);
+    SFM_REQUIRE(d->B >= 0, SFM_ERR_SHAPE, "%s: B=%d", who, d->B);
+    long long total = 0;
+    A.begin[0] = 0;
+    for (int s = 0; s < d->n_scales; ++s) {
+      SFM_REQUIRE(d->H[s] >= 1 && d->W[s] >= 1, SFM_ERR_SHAPE, "%s: scale %d: H=%d W=%d, need H,W >= 1", who, s, d->H[s], d->W[s]);
+      SFM_REQUIRE(3ll * d->H[s] * d->W[s] < (1ll << 31), SFM_ERR_SHAPE, "%s: scale %d: 3*H*W too large", who, s);
+      A.H[s] = d->H[s], A.W[s] = d->W[s];
+      total += (long long)d->B * tiles(s, A.H[s], A.W[s]);
+      SFM_REQUIRE(total < (1ll << 31), SFM_ERR_SHAPE, "%s: too many wavefront tiles (%lld): the grid would overflow", who, total);
+      A.begin[s + 1] = (int)total;
+    }
+  }
   A.B = d->B, A.n_img = d->n_img, A.n_scales = d->n_scales;
   SFM_REQUIRE(d->ssim_rate >= 0.f && d->ssim_rate <= 1.f, SFM_ERR_CONFIG, "%s: ssim_rate=%g, need 0 <= ssim_rate <= 1", who,
               (double)d->ssim_rate);
   A.w_l1 = (1.f - d->ssim_rate) / 3.f;
   A.w_ssim = d->ssim_rate / 3.f;
+  SFM_REQUIRE(padding == SFM_SSIM_PAD_ZERO || padding == SFM_SSIM_PAD_REFLECT, SFM_ERR_CONFIG, "%s: padding=%d", who, (int)padding);
+  if (padding == SFM_SSIM_PAD_REFLECT)
+    for (int s = 0; s < d->n_scales; ++s)
+      SFM_REQUIRE(d->H[s] >= 2 && d->W[s] >= 2, SFM_ERR_SHAPE, "%s: scale %d: H=%d W=%d, reflection padding needs H,W >= 2", who, s, d->H[s],
+                  d->W[s]);
   if (d->B == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
   for (int s = 0; s < d->n_scales; ++s) {
     SFM_REQUIRE(d->img[s], SFM_ERR_NULL, "%s: img[%d] is NULL", who, s);
@@ -311,30 +377,49 @@ static int photo_err_setup(PhotoErrArgs& A, const char* who, const SfmPhotoError
 
 static dim3 photo_err_grid(const PhotoErrArgs& A) { return dim3((unsigned)((A.begin[A.n_scales] + PE_WAVES - 1) / PE_WAVES)); }
 
+// the two calls, for either padding: the existing entry points pass SFM_SSIM_PAD_ZERO.  Without the SSIM term no window is formed
+// and the padding selects nothing.
+static int photo_err_fwd(const char* who, const SfmPhotoErrorDesc* d, const int32_t padding, void* stream) {
+  PhotoErrArgs A = {};
+  if (int e = photo_err_setup(A, who, d, false, padding)) return e;
+  if (d->B == 0) return SFM_OK;
+  const dim3 grid = photo_err_grid(A), block(PE_BLOCK);
+  const hipStream_t st = (hipStream_t)stream;
+  if (!(d->ssim_rate > 0.f)) hipLaunchKernelGGL((photo_err_fwd_kernel<false, false>), grid, block, 0, st, A);
+  else if (padding == SFM_SSIM_PAD_REFLECT) hipLaunchKernelGGL((photo_err_fwd_kernel<true, true>), grid, block, 0, st, A);
+  else hipLaunchKernelGGL((photo_err_fwd_kernel<true, false>), grid, block, 0, st, A);
+  return check_launch(who);
+}
+
+static int photo_err_bwd(const char* who, const SfmPhotoErrorDesc* d, const int32_t padding, void* stream) {
+  PhotoErrArgs A = {};
+  if (int e = photo_err_setup(A, who, d, true, padding)) return e;
+  if (d->B == 0) return SFM_OK;
+  const dim3 grid = photo_err_grid(A), block(PE_BLOCK);
+  const hipStream_t st = (hipStream_t)stream;
+  if (!(d->ssim_rate > 0.f)) hipLaunchKernelGGL((photo_err_bwd_kernel<false, false>), grid, block, 0, st, A);
+  else if (padding == SFM_SSIM_PAD_REFLECT) hipLaunchKernelGGL((photo_err_bwd_kernel<true, true>), grid, block, 0, st, A);
+  else hipLaunchKernelGGL((photo_err_bwd_kernel<true, false>), grid, block, 0, st, A);
+  return check_launch(who);
+}
+
 }  // namespace sfm
 
 using namespace sfm;
 
 extern "C" {
 
-int sfm_photo_error_fwd(const SfmPhotoErrorDesc* d, void* stream) {
-  const char* who = "sfm_photo_error_fwd";
-  PhotoErrArgs A = {};
-  if (int e = photo_err_setup(A, who, d, false)) return e;
-  if (d->B == 0) return SFM_OK;
-  if (d->ssim_rate > 0.f) hipLaunchKernelGGL(photo_err_fwd_kernel<true>, photo_err_grid(A), dim3(PE_BLOCK), 0, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL(photo_err_fwd_kernel<false>, photo_err_grid(A), dim3(PE_BLOCK), 0, (hipStream_t)stream, A);
-  return check_launch(who);
+int sfm_photo_error_fwd(const SfmPhotoErrorDesc* d, void* stream) { return photo_err_fwd("sfm_photo_error_fwd", d, SFM_SSIM_PAD_ZERO, stream); }
+
+int sfm_photo_error_bwd(const SfmPhotoErrorDesc* d, void* stream) { return photo_err_bwd("sfm_photo_error_bwd", d, SFM_SSIM_PAD_ZERO, stream); }
+
+// include/sfmwarp_conventions.h
+int sfm_photo_error_pad_fwd(const SfmPhotoErrorDesc* d, int32_t padding, void* stream) {
+  return photo_err_fwd("sfm_photo_error_pad_fwd", d, padding, stream);
 }
 
-int sfm_photo_error_bwd(const SfmPhotoErrorDesc* d, void* stream) {
-  const char* who = "sfm_photo_error_bwd";
-  PhotoErrArgs A = {};
-  if (int e = photo_err_setup(A, who, d, true)) return e;
-  if (d->B == 0) return SFM_OK;
-  if (d->ssim_rate > 0.f) hipLaunchKernelGGL(photo_err_bwd_kernel<true>, photo_err_grid(A), dim3(PE_BLOCK), 0, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL(photo_err_bwd_kernel<false>, photo_err_grid(A), dim3(PE_BLOCK), 0, (hipStream_t)stream, A);
-  return check_launch(who);
+int sfm_photo_error_pad_bwd(const SfmPhotoErrorDesc* d, int32_t padding, void* stream) {
+  return photo_err_bwd("sfm_photo_error_pad_bwd", d, padding, stream);
 }
 
 }  // extern "C"

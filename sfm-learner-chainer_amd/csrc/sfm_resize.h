@@ -1,6 +1,7 @@
 // F.resize_images, align-corners bilinear (models/base_model.py:70-72), per output element: ONE copy for every translation unit
 // that resamples -- sfm_ops.hip (resize forward and backward, the three pyramid kernels, augment) and sfm_warp_full_res.hip (the
-// disparity upsampled inside the warp, and its adjoint).  gfx950 only.
+// disparity upsampled inside the warp, and its adjoint).  Below them, under names of their own, the half-pixel taps that
+// sfm_warp_full_res.hip offers beside them (include/sfmwarp_conventions.h).  gfx950 only.
 #pragma once
 #include "sfm_common.h"
 
@@ -54,6 +55,41 @@ __device__ __forceinline__ int resize_first_at(const int k, const int n, const i
   int o = (int)fmin(ceil((double)k * inv_step), (double)on);
   while (o > 0 && resize_tap0(resize_coord(o - 1, step), n) >= k) --o;
   while (o < on && resize_tap0(resize_coord(o, step), n) < k) ++o;
+  return o;
+}
+
+// ------------------------------------------------------------------------------------------
+// Half-pixel bilinear, F.interpolate(mode="bilinear", align_corners=False) (include/sfmwarp_conventions.h): the coordinate and the
+// taps under names of their own; the blend and the read are resize_blend and resize_read above.  All float32, contraction off.
+// ------------------------------------------------------------------------------------------
+// max(scale * (o + 0.5) - 0.5, 0) with scale = (float)n / (float)on formed on the host: non-decreasing in o, every step rounds monotonically
+__device__ __forceinline__ float resize_hp_coord(const int o, const float scale) {
+#pragma clang fp contract(off)
+  const float c = scale * ((float)o + 0.5f);
+  return fmaxf(c - 0.5f, 0.0f);
+}
+
+// (x >= 0 and below n + 1 for every output; the clamp keeps an index in bounds whatever a caller passes)
+__device__ __forceinline__ int resize_hp_tap0(const float x, const int n) { return min(max((int)floorf(x), 0), n - 1); }
+
+__device__ __forceinline__ ResizeTap resize_hp_taps(const float u, const float v, const int H, const int W) {
+#pragma clang fp contract(off)
+  ResizeTap t;
+  t.u0 = resize_hp_tap0(u, W), t.v0 = resize_hp_tap0(v, H);
+  t.u1 = min(t.u0 + 1, W - 1), t.v1 = min(t.v0 + 1, H - 1);
+  t.wu1 = u - (float)t.u0, t.wv1 = v - (float)t.v0;
+  t.wu0 = 1.0f - t.wu1, t.wv0 = 1.0f - t.wv1;
+  return t;
+}
+
+// the first o in [0, on] with resize_hp_tap0(resize_hp_coord(o, scale), n) >= k (on: there is none); inv_scale = (float)on / (float)n
+// only places the first guess, (k + 0.5) / scale - 0.5: the two walks settle it on the coordinate the kernels use
+__device__ __forceinline__ int resize_hp_first_at(const int k, const int n, const int on, const float scale, const float inv_scale) {
+  if (k <= 0) return 0;
+  if (k > n - 1) return on;                      // tap0 never exceeds n - 1
+  int o = (int)fminf(fmaxf(ceilf(((float)k + 0.5f) * inv_scale - 0.5f), 0.0f), (float)on);
+  while (o > 0 && resize_hp_tap0(resize_hp_coord(o - 1, scale), n) >= k) --o;
+  while (o < on && resize_hp_tap0(resize_hp_coord(o, scale), n) < k) ++o;
   return o;
 }
 

@@ -7,10 +7,15 @@
 // One grid covers every (scale, sample, 256-pixel block): all scales have the full resolution, so block index = (s * B + b) * nblk
 // + block.  A block builds the geometry of each of its sources once -- the same for every scale: one camera --, a thread forms
 // its disparity once from the four low-resolution taps and loops over the sources.
+//
+// HP (include/sfmwarp_conventions.h) is a template parameter of the two pixel kernels and of the gather: the four taps and their
+// weights are the half-pixel ones of F.interpolate(align_corners=False) (sfm_resize.h), everything else is the same code; the
+// align-corners instantiations keep theirs.
 #include "sfm_common.h"
 #include "sfm_resize.h"
 #include "sfm_warp_pixel.h"
 #include "../../include/sfmwarp_full_res.h"
+#include "../../include/sfmwarp_conventions.h"
 
 namespace sfm {
 
@@ -32,6 +37,8 @@ struct WarpFullArgs {
   // the upsampling's steps as resize_fwd_kernel forms them, (h-1)/(H-1), and their reciprocals (0 for a step of 0) as sfm_resize_bwd
   // forms them: all in double on the host
   double step_u[SFM_MAX_SCALES], step_v[SFM_MAX_SCALES], inv_u[SFM_MAX_SCALES], inv_v[SFM_MAX_SCALES];
+  // the half-pixel upsampling's scales, (float)w / (float)W, and the reciprocal ratios (a first guess of the gather only): float32, host
+  float hp_u[SFM_MAX_SCALES], hp_v[SFM_MAX_SCALES], hp_inv_u[SFM_MAX_SCALES], hp_inv_v[SFM_MAX_SCALES];
   long long gather[SFM_MAX_SCALES + 1];   // prefix sums of B * h * w over the RESAMPLED scales (the others count 0)
   int h[SFM_MAX_SCALES], w[SFM_MAX_SCALES];
   bool resampled[SFM_MAX_SCALES];
@@ -66,18 +73,25 @@ __device__ __forceinline__ void warp_full_geoms(const WarpFullArgs& A, const War
   __syncthreads();
 }
 
-// up[s][b, y, x]: the element itself at equal sizes, else resize_fwd_kernel's value (W, H >= 3: more than one output per axis)
+// up[s][b, y, x]: the element itself at equal sizes, else resize_fwd_kernel's value (W, H >= 3: more than one output per axis) or,
+// HP, the half-pixel value of include/sfmwarp_conventions.h
+template <bool HP>
 __device__ __forceinline__ float warp_full_disp(const WarpFullArgs& A, const WarpFullBlock& w, const int y, const int x, const int j) {
 #pragma clang fp contract(off)
   const int h = A.h[w.s], ww = A.w[w.s];
   const float* disp = A.disp[w.s] + (size_t)w.b * h * ww;
   if (!A.resampled[w.s]) return disp[j];
+  if constexpr (HP) {
+    const float u = resize_hp_coord(x, A.hp_u[w.s]);
+    const float v = resize_hp_coord(y, A.hp_v[w.s]);
+    return resize_read(resize_hp_taps(u, v, h, ww), disp, ww);
+  }
   const float u = resize_coord(x, A.step_u[w.s]);
   const float v = resize_coord(y, A.step_v[w.s]);
   return resize_read(resize_taps(u, v, h, ww), disp, ww);
 }
 
-template <bool HWC>
+template <bool HWC, bool HP = false>
 __global__ void __launch_bounds__(WF_BLOCK) warp_full_fwd_kernel(const WarpFullArgs A) {
 #pragma clang fp contract(off)
   __shared__ Geom g[SFM_MAX_SRC];
@@ -87,7 +101,7 @@ __global__ void __launch_bounds__(WF_BLOCK) warp_full_fwd_kernel(const WarpFullA
   const int j = w.blk * WF_BLOCK + threadIdx.x;
   if (j >= P) return;
   const int y = j / W, x = j - y * W;
-  const float depth = 1.0f / warp_full_disp(A, w, y, x, j);      // models/base_model.py:60
+  const float depth = 1.0f / warp_full_disp<HP>(A, w, y, x, j);      // models/base_model.py:60
   const float D[3] = {depth, depth, depth};
   float* valid = A.valid[w.s];
   for (int i = 0; i < A.n_src; ++i) {
@@ -106,7 +120,7 @@ __global__ void __launch_bounds__(WF_BLOCK) warp_full_fwd_kernel(const WarpFullA
   }
 }
 
-template <bool HWC>
+template <bool HWC, bool HP = false>
 __global__ void __launch_bounds__(WF_BLOCK) warp_full_bwd_kernel(const WarpFullArgs A) {
 #pragma clang fp contract(off)
   __shared__ Geom g[SFM_MAX_SRC];
@@ -118,7 +132,7 @@ __global__ void __launch_bounds__(WF_BLOCK) warp_full_bwd_kernel(const WarpFullA
   const bool have = j < P;                       // no early exit: the lanes of a wave add up their sums below
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int y = j / W, x = j - y * W;
-  const float disp = have ? warp_full_disp(A, w, y, x, j) : 1.0f;
+  const float disp = have ? warp_full_disp<HP>(A, w, y, x, j) : 1.0f;
   const float depth = 1.0f / disp;               // models/base_model.py:60
   const float D[3] = {depth, depth, depth};
   float g_depth = 0.f;
@@ -153,7 +167,9 @@ __global__ void __launch_bounds__(WF_BLOCK) warp_full_bwd_kernel(const WarpFullA
 }
 
 // d_disp[s] = R_s^T d_up[s] for every resampled scale in one launch: resize_bwd_kernel with one term, one thread per element of
-// d_disp[s], which adds the full-resolution values whose taps touch it in ascending (oy, ox)
+// d_disp[s], which adds the full-resolution values whose taps touch it in ascending (oy, ox).  HP: the same sum over the half-pixel
+// taps -- the first outputs that reach a tap found on the float32 coordinate the forward uses, which is non-decreasing in the index
+template <bool HP = false>
 __global__ void __launch_bounds__(256) warp_full_gather_kernel(const WarpFullArgs A) {
 #pragma clang fp contract(off)
   const long long jj = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -164,6 +180,24 @@ __global__ void __launch_bounds__(256) warp_full_gather_kernel(const WarpFullArg
   const int HW = H * W;
   const int nc = (int)(j / HW), r = (int)(j - (long long)nc * HW);
   const int iy = r / W, ix = r - iy * W;
+  if constexpr (HP) {
+    const float* g = A.d_up[s] + (size_t)nc * oH * oW;
+    float acc = 0.f;
+    const float su = A.hp_u[s], sv = A.hp_v[s];
+    const int x0 = resize_hp_first_at(ix - 1, W, oW, su, A.hp_inv_u[s]), x1 = resize_hp_first_at(ix + 1, W, oW, su, A.hp_inv_u[s]);
+    const int y0 = resize_hp_first_at(iy - 1, H, oH, sv, A.hp_inv_v[s]), y1 = resize_hp_first_at(iy + 1, H, oH, sv, A.hp_inv_v[s]);
+    for (int oy = y0; oy < y1; ++oy) {
+      const float v = resize_hp_coord(oy, sv);
+      for (int ox = x0; ox < x1; ++ox) {
+        const ResizeTap t = resize_hp_taps(resize_hp_coord(ox, su), v, H, W);
+        const float wu = (t.u0 == ix ? t.wu0 : 0.f) + (t.u1 == ix ? t.wu1 : 0.f);
+        const float wv = (t.v0 == iy ? t.wv0 : 0.f) + (t.v1 == iy ? t.wv1 : 0.f);
+        acc = acc + g[oy * oW + ox] * (wv * wu);
+      }
+    }
+    A.d_disp[s][j] = acc;
+    return;
+  }
   const double su = A.step_u[s], sv = A.step_v[s];
   const int x0 = resize_first_at(ix - 1, W, oW, su, A.inv_u[s]), x1 = resize_first_at(ix + 1, W, oW, su, A.inv_u[s]);
   const int y0 = resize_first_at(iy - 1, H, oH, sv, A.inv_v[s]), y1 = resize_first_at(iy + 1, H, oH, sv, A.inv_v[s]);
@@ -208,7 +242,7 @@ __global__ void __launch_bounds__(64) warp_full_fold_kernel(const WarpFullArgs A
 }
 
 // The sizes and the layout, in the order the header states them: everything the workspace query needs, no pointer looked at.
-static int warp_full_shape(WarpFullArgs& A, const char* who, const SfmWarpFullResDesc* d) {
+static int warp_full_shape(WarpFullArgs& A, const char* who, const SfmWarpFullResDesc* d, const int32_t upsample = SFM_UPSAMPLE_ALIGN_CORNERS) {
   SFM_REQUIRE(d, SFM_ERR_NULL, "%s: NULL descriptor", who);
   SFM_REQUIRE(d->n_src >= 1 && d->n_src <= SFM_MAX_SRC, SFM_ERR_SHAPE, "%s: n_src=%d, need 1..%d", who, d->n_src, SFM_MAX_SRC);
   SFM_REQUIRE(d->n_scales >= 1 && d->n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "%s: n_scales=%d, need 1..%d", who, d->n_scales,
@@ -231,12 +265,16 @@ static int warp_full_shape(WarpFullArgs& A, const char* who, const SfmWarpFullRe
     A.step_v[s] = (double)(h - 1) / (double)(d->H - 1);
     A.inv_u[s] = A.step_u[s] > 0.0 ? 1.0 / A.step_u[s] : 0.0;
     A.inv_v[s] = A.step_v[s] > 0.0 ? 1.0 / A.step_v[s] : 0.0;
+    A.hp_u[s] = (float)w / (float)d->W, A.hp_v[s] = (float)h / (float)d->H;
+    A.hp_inv_u[s] = (float)d->W / (float)w, A.hp_inv_v[s] = (float)d->H / (float)h;
   }
   const long long blocks = (long long)d->n_scales * d->B * A.nblk, gather_blocks = (A.gather[d->n_scales] + 255) / 256;
   SFM_REQUIRE(blocks < (1ll << 31), SFM_ERR_SHAPE, "%s: too many 256-pixel blocks (%lld)", who, blocks);
   SFM_REQUIRE(gather_blocks < (1ll << 31), SFM_ERR_SHAPE, "%s: too many 256-element blocks of d_disp (%lld)", who, gather_blocks);
   SFM_REQUIRE(d->image_layout == SFM_LAYOUT_PLANAR || d->image_layout == SFM_LAYOUT_HWC, SFM_ERR_CONFIG, "%s: image_layout=%d", who,
               d->image_layout);
+  SFM_REQUIRE(upsample == SFM_UPSAMPLE_ALIGN_CORNERS || upsample == SFM_UPSAMPLE_HALF_PIXEL, SFM_ERR_CONFIG, "%s: upsample=%d", who,
+              (int)upsample);
   return SFM_OK;
 }
 
@@ -273,34 +311,28 @@ static size_t warp_full_ws_bytes(const WarpFullArgs& A) {
   return need ? (need + 255) / 256 * 256 : 256;
 }
 
-}  // namespace sfm
-
-using namespace sfm;
-
-extern "C" {
-
-int sfm_warp_full_res_fwd(const SfmWarpFullResDesc* d, void* stream) {
-  const char* who = "sfm_warp_full_res_fwd";
+// the three calls, for either upsampling: the existing entry points pass SFM_UPSAMPLE_ALIGN_CORNERS
+static int warp_full_fwd(const char* who, const SfmWarpFullResDesc* d, const int32_t upsample, void* stream) {
   WarpFullArgs A;
-  if (int e = warp_full_shape(A, who, d)) return e;
+  if (int e = warp_full_shape(A, who, d, upsample)) return e;
   if (d->B == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
   if (int e = warp_full_pointers(A, who, d, false)) return e;
   const dim3 grid(A.n_scales * A.B * A.nblk);
-  if (d->image_layout == SFM_LAYOUT_HWC) hipLaunchKernelGGL(warp_full_fwd_kernel<true>, grid, dim3(WF_BLOCK), 0, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL(warp_full_fwd_kernel<false>, grid, dim3(WF_BLOCK), 0, (hipStream_t)stream, A);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool hwc = d->image_layout == SFM_LAYOUT_HWC;
+  if (upsample == SFM_UPSAMPLE_HALF_PIXEL) {
+    if (hwc) hipLaunchKernelGGL((warp_full_fwd_kernel<true, true>), grid, dim3(WF_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL((warp_full_fwd_kernel<false, true>), grid, dim3(WF_BLOCK), 0, st, A);
+  } else {
+    if (hwc) hipLaunchKernelGGL((warp_full_fwd_kernel<true, false>), grid, dim3(WF_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL((warp_full_fwd_kernel<false, false>), grid, dim3(WF_BLOCK), 0, st, A);
+  }
   return check_launch(who);
 }
 
-size_t sfm_warp_full_res_bwd_workspace_bytes(const SfmWarpFullResDesc* d) {
+static int warp_full_bwd(const char* who, const SfmWarpFullResDesc* d, const int32_t upsample, void* ws, size_t ws_bytes, void* stream) {
   WarpFullArgs A;
-  if (warp_full_shape(A, "sfm_warp_full_res_bwd_workspace_bytes", d)) return 0;
-  return warp_full_ws_bytes(A);
-}
-
-int sfm_warp_full_res_bwd(const SfmWarpFullResDesc* d, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "sfm_warp_full_res_bwd";
-  WarpFullArgs A;
-  if (int e = warp_full_shape(A, who, d)) return e;
+  if (int e = warp_full_shape(A, who, d, upsample)) return e;
   if (d->B == 0) return SFM_OK;
   if (int e = warp_full_pointers(A, who, d, true)) return e;
   const size_t need = warp_full_ws_bytes(A);
@@ -312,12 +344,57 @@ int sfm_warp_full_res_bwd(const SfmWarpFullResDesc* d, void* ws, size_t ws_bytes
     if (A.resampled[s]) A.d_up[s] = up, up += (size_t)A.B * A.H * A.W;
   const dim3 grid(A.n_scales * A.B * A.nblk);
   const hipStream_t st = (hipStream_t)stream;
-  if (d->image_layout == SFM_LAYOUT_HWC) hipLaunchKernelGGL(warp_full_bwd_kernel<true>, grid, dim3(WF_BLOCK), 0, st, A);
-  else hipLaunchKernelGGL(warp_full_bwd_kernel<false>, grid, dim3(WF_BLOCK), 0, st, A);
+  const bool hwc = d->image_layout == SFM_LAYOUT_HWC, hp = upsample == SFM_UPSAMPLE_HALF_PIXEL;
+  if (hp) {
+    if (hwc) hipLaunchKernelGGL((warp_full_bwd_kernel<true, true>), grid, dim3(WF_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL((warp_full_bwd_kernel<false, true>), grid, dim3(WF_BLOCK), 0, st, A);
+  } else {
+    if (hwc) hipLaunchKernelGGL((warp_full_bwd_kernel<true, false>), grid, dim3(WF_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL((warp_full_bwd_kernel<false, false>), grid, dim3(WF_BLOCK), 0, st, A);
+  }
   const long long n_gather = A.gather[A.n_scales];
-  if (n_gather > 0) hipLaunchKernelGGL(warp_full_gather_kernel, dim3((unsigned)((n_gather + 255) / 256)), dim3(256), 0, st, A);
+  if (n_gather > 0) {
+    const dim3 gg((unsigned)((n_gather + 255) / 256));
+    if (hp) hipLaunchKernelGGL(warp_full_gather_kernel<true>, gg, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(warp_full_gather_kernel<false>, gg, dim3(256), 0, st, A);
+  }
   hipLaunchKernelGGL(warp_full_fold_kernel, dim3(d->B * d->n_src), dim3(64), 0, st, A);
   return check_launch(who);
+}
+
+}  // namespace sfm
+
+using namespace sfm;
+
+extern "C" {
+
+int sfm_warp_full_res_fwd(const SfmWarpFullResDesc* d, void* stream) {
+  return warp_full_fwd("sfm_warp_full_res_fwd", d, SFM_UPSAMPLE_ALIGN_CORNERS, stream);
+}
+
+size_t sfm_warp_full_res_bwd_workspace_bytes(const SfmWarpFullResDesc* d) {
+  WarpFullArgs A;
+  if (warp_full_shape(A, "sfm_warp_full_res_bwd_workspace_bytes", d)) return 0;
+  return warp_full_ws_bytes(A);
+}
+
+int sfm_warp_full_res_bwd(const SfmWarpFullResDesc* d, void* ws, size_t ws_bytes, void* stream) {
+  return warp_full_bwd("sfm_warp_full_res_bwd", d, SFM_UPSAMPLE_ALIGN_CORNERS, ws, ws_bytes, stream);
+}
+
+// include/sfmwarp_conventions.h
+int sfm_warp_full_res_up_fwd(const SfmWarpFullResDesc* d, int32_t upsample, void* stream) {
+  return warp_full_fwd("sfm_warp_full_res_up_fwd", d, upsample, stream);
+}
+
+size_t sfm_warp_full_res_up_bwd_workspace_bytes(const SfmWarpFullResDesc* d, int32_t upsample) {
+  WarpFullArgs A;
+  if (warp_full_shape(A, "sfm_warp_full_res_up_bwd_workspace_bytes", d, upsample)) return 0;
+  return warp_full_ws_bytes(A);
+}
+
+int sfm_warp_full_res_up_bwd(const SfmWarpFullResDesc* d, int32_t upsample, void* ws, size_t ws_bytes, void* stream) {
+  return warp_full_bwd("sfm_warp_full_res_up_bwd", d, upsample, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

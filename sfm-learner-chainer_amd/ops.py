@@ -558,25 +558,40 @@ def _warp_full_res_desc(src, disps, poses, K, layout):
     return d, (src, disps, poses, K), B, n_src, (H, W), hw, dev
 
 
-def warp_full_res_fwd(src, disps, poses, K, layout, want_valid=False):
+def _warp_full_res_calls(upsample):
+    """(fwd, workspace query, bwd) as callables of the existing signatures: the existing symbols for "align_corners", those of
+    include/sfmwarp_conventions.h with the value bound for "half_pixel"; an unknown name is a ValueError"""
+    if upsample == "align_corners":
+        return lib.sfm_warp_full_res_fwd, lib.sfm_warp_full_res_bwd_workspace_bytes, lib.sfm_warp_full_res_bwd
+    up = _lib.upsample_id(upsample)
+    return (lambda d, *rest: lib.sfm_warp_full_res_up_fwd(d, up, *rest),
+            lambda d: lib.sfm_warp_full_res_up_bwd_workspace_bytes(d, up),
+            lambda d, *rest: lib.sfm_warp_full_res_up_bwd(d, up, *rest))
+
+
+def warp_full_res_fwd(src, disps, poses, K, layout, want_valid=False, upsample="align_corners"):
     """ONE full-resolution source set warped with the disparity of every scale, each upsampled to (H, W) inside the kernel, in ONE
     launch (sfm_warp_full_res_fwd): src (B,3*n_src,H,W) for layout "planar" or (B,n_src,H,W,3) for "hwc", disps[s] (B,1,h_s,w_s) of any
     sizes, poses[i] (B,6), K (B,3,3) -> [warped_s (B,n_src,3,H,W)]: `warp_pyramid_fwd` at equal sizes on `resize` of each disparity
-    (itself where it has the full size), bit for bit; with `want_valid` also [valid_s (B,n_src,H,W)]."""
+    (itself where it has the full size), bit for bit; with `want_valid` also [valid_s (B,n_src,H,W)].  upsample="half_pixel": each
+    disparity upsampled as F.interpolate(mode="bilinear", align_corners=False) does instead (sfm_warp_full_res_up_fwd)."""
+    fwd = _warp_full_res_calls(upsample)[0]
     d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout)
     warped = _empty([(B, n_src, 3, H, W)] * len(hw), dev)
     valid = _empty([(B, n_src, H, W)] * len(hw), dev) if want_valid else None
     _point(d.warped, warped)
     _point(d.valid, valid or ())
-    _launch(dev, lib.sfm_warp_full_res_fwd, C.byref(d))
+    _launch(dev, fwd, C.byref(d))
     return (warped, valid) if want_valid else warped
 
 
-def warp_full_res_bwd(src, disps, poses, K, layout, g_warped, ws=None):
+def warp_full_res_bwd(src, disps, poses, K, layout, g_warped, ws=None, upsample="align_corners"):
     """The backward of `warp_full_res_fwd` for the upstream gradients g_warped[s] (B,n_src,3,H,W): one launch over the pixels, one
     that gathers every low-resolution gradient and a small fold (sfm_warp_full_res_bwd) -> ([d_disp_s (B,1,h_s,w_s)], [d_pose_i
     (B,6)]): `warp_pyramid_bwd` at equal sizes followed by `resize_bwd` of each d_disp, bit for bit.  No atomics: the same bits on
-    every call, whatever `ws` (the caller's workspace, or None for a fresh one) held."""
+    every call, whatever `ws` (the caller's workspace, or None for a fresh one) held.  upsample="half_pixel": the backward of that
+    forward (sfm_warp_full_res_up_bwd), each d_disp the adjoint of the half-pixel upsampling; the workspace is the same."""
+    _, query, bwd = _warp_full_res_calls(upsample)
     d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout)
     if len(g_warped) != len(hw):
         raise TypeError("g_warped needs one entry per scale")
@@ -588,12 +603,12 @@ def warp_full_res_bwd(src, disps, poses, K, layout, g_warped, ws=None):
     d_poses = _empty([(B, 6)] * n_src, dev)
     for field, arrays in ((d.g_warped, g_warped), (d.d_disp, d_disps), (d.d_pose, d_poses)):
         _point(field, arrays)
-    nbytes = lib.sfm_warp_full_res_bwd_workspace_bytes(C.byref(d))
+    nbytes = query(C.byref(d))
     if nbytes == 0:
-        check(lib.sfm_warp_full_res_bwd(C.byref(d), None, 0, None))   # re-run the validation for its message
+        check(bwd(C.byref(d), None, 0, None))   # re-run the validation for its message
         raise ValueError(_lib.last_error() or "invalid full-resolution warp descriptor")
     ws, ptr, have = _place_workspace(ws, nbytes, dev)
-    _launch(dev, lib.sfm_warp_full_res_bwd, C.byref(d), C.c_void_p(ptr), have)
+    _launch(dev, bwd, C.byref(d), C.c_void_p(ptr), have)
     return d_disps, d_poses
 
 
@@ -626,21 +641,33 @@ def _photo_error_desc(imgs, tgts, ssim_rate):
     return d, (imgs, tgts), B, n_img, hw, dev
 
 
-def photo_error_fwd(imgs, tgts, ssim_rate):
+def _photo_error_calls(padding):
+    """(fwd, bwd) as callables of the existing signatures: the existing symbols for "zero", those of include/sfmwarp_conventions.h
+    with the value bound for "reflect"; an unknown name is a ValueError"""
+    if padding == "zero":
+        return lib.sfm_photo_error_fwd, lib.sfm_photo_error_bwd
+    pad = _lib.ssim_padding_id(padding)
+    return (lambda d, *rest: lib.sfm_photo_error_pad_fwd(d, pad, *rest)), (lambda d, *rest: lib.sfm_photo_error_pad_bwd(d, pad, *rest))
+
+
+def photo_error_fwd(imgs, tgts, ssim_rate, padding="zero"):
     """The photometric error map of every (scale, image) of a step in ONE launch (sfm_photo_error_fwd): imgs[s] (B,n_img,3,h,w) --
     what `warp_pyramid_fwd` returns, or the planar source pyramid viewed so --, tgts[s] (B,3,h,w) -> [err_s (B,n_img,h,w)],
     err = (1 - ssim_rate) * mean_c |X - Y| + ssim_rate * mean_c compute_ssim(X, Y) of models/base_model.py:126-142 per pixel.  A
-    rejection by the library (ssim_rate outside [0,1]) is a ValueError with sfm_last_error() as its message."""
+    rejection by the library (ssim_rate outside [0,1]) is a ValueError with sfm_last_error() as its message.  padding="reflect": the
+    3x3 SSIM window over the image extended by ReflectionPad2d(1) (sfm_photo_error_pad_fwd; every h, w >= 2, else TypeError)."""
+    fwd = _photo_error_calls(padding)[0]
     d, keep, B, n_img, hw, dev = _photo_error_desc(imgs, tgts, ssim_rate)
     err = _empty([(B, n_img, h, w) for h, w in hw], dev)
     _point(d.err, err)
-    _launch(dev, lib.sfm_photo_error_fwd, C.byref(d))
+    _launch(dev, fwd, C.byref(d))
     return err
 
 
-def photo_error_bwd(imgs, tgts, ssim_rate, g_err):
+def photo_error_bwd(imgs, tgts, ssim_rate, g_err, padding="zero"):
     """The backward of `photo_error_fwd` for the upstream gradients g_err[s] (B,n_img,h,w), ONE launch (sfm_photo_error_bwd) ->
-    [d_img_s (B,n_img,3,h,w)].  The targets are constants.  No atomics: the same bits on every call."""
+    [d_img_s (B,n_img,3,h,w)].  The targets are constants.  No atomics: the same bits on every call.  `padding` as in the forward."""
+    bwd = _photo_error_calls(padding)[1]
     d, keep, B, n_img, hw, dev = _photo_error_desc(imgs, tgts, ssim_rate)
     if not isinstance(g_err, (list, tuple)) or len(g_err) != len(hw):
         raise TypeError("g_err needs one entry per scale")
@@ -651,7 +678,7 @@ def photo_error_bwd(imgs, tgts, ssim_rate, g_err):
     d_imgs = _empty([(B, n_img, 3, h, w) for h, w in hw], dev)
     for field, arrays in ((d.g_err, g_err), (d.d_img, d_imgs)):
         _point(field, arrays)
-    _launch(dev, lib.sfm_photo_error_bwd, C.byref(d))
+    _launch(dev, bwd, C.byref(d))
     return d_imgs
 
 

@@ -570,13 +570,13 @@ def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=F
 
 class _WarpFullRes(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, src, K, S, want_valid, *arrays):
+    def forward(ctx, src, K, S, want_valid, upsample, *arrays):
         disps, poses = list(arrays[:S]), list(arrays[S:])
         hwc = ops.pyramid_hwc(src, 1)[0]
-        out = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", want_valid)
+        out = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", want_valid, upsample=upsample)
         warped, valid = out if want_valid else (out, [])
         ctx.save_for_backward(K, hwc, *disps, *poses)
-        ctx.S = S
+        ctx.S, ctx.upsample = S, upsample
         ctx.mark_non_differentiable(*valid)
         ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
         return tuple(warped) + tuple(valid)
@@ -589,8 +589,8 @@ class _WarpFullRes(torch.autograd.Function):
         B, n_src, H, W = hwc.shape[:4]
         g = [torch.zeros((B, n_src, 3, H, W), dtype=torch.float32, device=hwc.device) if gr is None
              else gr.to(torch.float32).contiguous() for gr in grads[:S]]
-        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", g)
-        return (None, None, None, None) + tuple(d_disps) + tuple(d_poses)
+        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", g, upsample=ctx.upsample)
+        return (None, None, None, None, None) + tuple(d_disps) + tuple(d_poses)
 
 
 def _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, who):
@@ -627,7 +627,7 @@ def _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, who):
     return src, K, disps, poses
 
 
-def warp_full_res(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False):
+def warp_full_res(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False, upsample="align_corners"):
     """Monodepth2's "full-resolution multi-scale" warp: the disparity of every scale upsampled to the input resolution and the
     FULL-RESOLUTION sources warped with it through the full-resolution camera -- what `resize_images` per scale followed by
     `projective_inverse_warp` per (scale, source) computes, in one launch and without a full-resolution copy of any disparity.
@@ -644,21 +644,26 @@ def warp_full_res(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=
 
     Two launches forward (the pixel-interleaved copy of the sources, the warp of all scales and sources); backward one launch over
     the pixels, one that gathers the gradient of every low-resolution disparity and a small fold, whatever S and n_src are.  No
-    atomics: the same bits on every call.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture."""
+    atomics: the same bits on every call.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture.
+
+    upsample="half_pixel" is Monodepth2's own upsampling instead: every resampled disparity is F.interpolate(pred_disps[s], (H, W),
+    mode="bilinear", align_corners=False) -- half-pixel centres -- formed inside the same launch, its gradient the adjoint of that map
+    in the same gather launch.  The launches, the workspace and the determinism are those of the default; any other name is a ValueError."""
+    _lib.upsample_id(upsample)
     src, K, disps, poses = _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, "warp_full_res")
     B, n_src, _, H, W = src.shape
     S = len(disps)
-    out = _WarpFullRes.apply(src.detach().view(B, 3 * n_src, H, W), K, S, bool(return_valid), *disps, *poses)
+    out = _WarpFullRes.apply(src.detach().view(B, 3 * n_src, H, W), K, S, bool(return_valid), upsample, *disps, *poses)
     return (list(out[:S]), list(out[S:])) if return_valid else list(out)
 
 
 class _PhotoError(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ssim_rate, S, *arrays):
+    def forward(ctx, ssim_rate, padding, S, *arrays):
         imgs, tgts = list(arrays[:S]), list(arrays[S:])
-        err = ops.photo_error_fwd(imgs, tgts, ssim_rate)
+        err = ops.photo_error_fwd(imgs, tgts, ssim_rate, padding)
         ctx.save_for_backward(*imgs, *tgts)
-        ctx.S, ctx.ssim_rate = S, ssim_rate
+        ctx.S, ctx.ssim_rate, ctx.padding = S, ssim_rate, padding
         ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
         return tuple(err)
 
@@ -668,11 +673,11 @@ class _PhotoError(torch.autograd.Function):
         imgs, tgts = list(ctx.saved_tensors[:S]), list(ctx.saved_tensors[S:])
         g = [torch.zeros(x.shape[:2] + x.shape[3:], dtype=torch.float32, device=x.device) if gr is None
              else gr.to(torch.float32).contiguous() for gr, x in zip(grads, imgs)]
-        d_imgs = ops.photo_error_bwd(imgs, tgts, ctx.ssim_rate, g)
-        return (None, None) + tuple(d_imgs) + (None,) * S
+        d_imgs = ops.photo_error_bwd(imgs, tgts, ctx.ssim_rate, g, ctx.padding)
+        return (None, None, None) + tuple(d_imgs) + (None,) * S
 
 
-def photometric_error(imgs, tgt, *, ssim_rate):
+def photometric_error(imgs, tgt, *, ssim_rate, padding="zero"):
     """The per-pixel photometric error of every (scale, image) of a step -- ssim_rate * compute_ssim + (1 - ssim_rate) * |.| of
     models/base_model.py:96,126-142 before any mean, averaged over the three channels -- as differentiable maps: the stage between
     `warp_pyramid` and a minimum over the sources, an auto-mask or a robust penalty of your own.
@@ -684,13 +689,17 @@ def photometric_error(imgs, tgt, *, ssim_rate):
       h_s, w_s must be H >> s, W >> s -- or a list of S per-scale tensors (B,3,h_s,w_s).  A constant: no gradient flows to it;
     ssim_rate: alpha in [0,1]; 0 is the mean absolute difference alone (no SSIM code runs), 1 the SSIM term alone.
 
-    Returns a list of S maps (B,n,h_s,w_s) in [0,1] for images in [-1,1].  The SSIM window is the reference's zero-padded 3x3
-    average (not Monodepth2's reflection padding), and nothing is masked: the zeros of out-of-view pixels take part in their
-    neighbours' windows as in the reference -- `warp_pyramid(..., return_valid=True)` has the mask.
+    padding: "zero", the reference's SSIM window -- a zero-padded 3x3 average, divided by 9 at the border too --, or "reflect",
+      Monodepth2's: the 3x3 average over the image extended by one pixel of reflection, ReflectionPad2d(1) + AvgPool2d(3, 1), so that
+      every window holds nine real values (every h_s, w_s >= 2, else TypeError).  Any other name is a ValueError.
+
+    Returns a list of S maps (B,n,h_s,w_s) in [0,1] for images in [-1,1].  Nothing is masked: the zeros of out-of-view pixels take
+    part in their neighbours' windows as in the reference -- `warp_pyramid(..., return_valid=True)` has the mask.
 
     One launch forward and one backward, whatever S and n are (plus the pyramid launch for a single `tgt`).  The gradient goes to
     `imgs` only; if none of them requires one, nothing is recorded.  Nothing reads a device value on the host: it runs under
     torch.cuda.graph capture."""
+    _lib.ssim_padding_id(padding)
     if not isinstance(imgs, (list, tuple)):
         raise TypeError("imgs must be a list of (B,n,3,h,w) tensors, one per scale")
     S = len(imgs)
@@ -724,7 +733,7 @@ def photometric_error(imgs, tgt, *, ssim_rate):
             raise TypeError("tgt[%d] must be (B,3,h,w) = %s, got %s" % (s, (B, 3) + tuple(x.shape[3:]), tuple(y.shape)))
         if x.device != xs[0].device or y.device != xs[0].device:
             raise TypeError("every array must live on %s" % (xs[0].device,))
-    return list(_PhotoError.apply(float(ssim_rate), S, *xs, *[y.detach() for y in tgts]))
+    return list(_PhotoError.apply(float(ssim_rate), padding, S, *xs, *[y.detach() for y in tgts]))
 
 
 def _scale_weights(weights, S):
@@ -882,24 +891,24 @@ class _MinReprojLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tgt, src, K, cfg, S, *arrays):
-        ssim_rate, auto_mask, weights, norm, smooth = cfg
+        ssim_rate, auto_mask, weights, norm, smooth, pad, _ = cfg
         disps, poses = list(arrays[:S]), list(arrays[S:])
         B, n_src = src.shape[0], len(poses)
         pyr = ops.pyramid_hwc(src, S)
         warped, valid = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", True)
         tgts = ops.pyramid(tgt, S)
-        errs = ops.photo_error_fwd(warped, tgts, ssim_rate)
+        errs = ops.photo_error_fwd(warped, tgts, ssim_rate, pad)
         idents = None
         if auto_mask:     # the identity reprojection: the planar source pyramid is (B,n_src,3,h,w) byte for byte
-            idents = ops.photo_error_fwd([p.view(B, n_src, 3, p.shape[2], p.shape[3]) for p in ops.pyramid(src, S)], tgts, ssim_rate)
+            idents = ops.photo_error_fwd([p.view(B, n_src, 3, p.shape[2], p.shape[3]) for p in ops.pyramid(src, S)], tgts, ssim_rate, pad)
         loss, count, winners = ops.min_reproj_fwd(errs, valid, idents, weights, norm)
         if smooth is None:
             ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners)
-            ctx.cfg = (S, n_src, ssim_rate, weights, norm, None)
+            ctx.cfg, ctx.pad = (S, n_src, ssim_rate, weights, norm, None), pad
             return loss[S]
         sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)      # on the target pyramid this node holds anyway
         ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners, stats)
-        ctx.cfg = (S, n_src, ssim_rate, weights, norm, smooth)
+        ctx.cfg, ctx.pad = (S, n_src, ssim_rate, weights, norm, smooth), pad
         return loss[S] + sm_loss[S]
 
     @staticmethod
@@ -913,7 +922,7 @@ class _MinReprojLoss(torch.autograd.Function):
         warped, tgts, winners = rest[:S], rest[S:2 * S], rest[2 * S:3 * S]
         g_loss = _g_loss(S, g_total, None, count.device)
         g_errs = ops.min_reproj_bwd(winners, count, g_loss, n_src, weights, norm, [tuple(t.shape[2:]) for t in disps])
-        d_warped = ops.photo_error_bwd(warped, tgts, ssim_rate, g_errs)
+        d_warped = ops.photo_error_bwd(warped, tgts, ssim_rate, g_errs, ctx.pad)
         d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", d_warped)
         if smooth is not None:      # the smoothness gradient is added in place by its kernel: no aten call
             ops.disp_smooth_bwd(disps, tgts, rest[3 * S], g_loss, *smooth, out=d_disps)
@@ -926,25 +935,25 @@ class _MinReprojLossFullRes(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tgt, src, K, cfg, S, *arrays):
-        ssim_rate, auto_mask, weights, norm, smooth = cfg
+        ssim_rate, auto_mask, weights, norm, smooth, pad, up = cfg
         disps, poses = list(arrays[:S]), list(arrays[S:])
         B, n_src = src.shape[0], len(poses)
         H, W = tgt.shape[2:]
         hwc = ops.pyramid_hwc(src, 1)[0]
-        warped, valid = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", True)
-        errs = ops.photo_error_fwd(warped, [tgt] * S, ssim_rate)
+        warped, valid = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", True, upsample=up)
+        errs = ops.photo_error_fwd(warped, [tgt] * S, ssim_rate, pad)
         idents = None
         if auto_mask:     # the identity reprojection, ONCE: the target and the unwarped sources are the same at every scale
-            idents = ops.photo_error_fwd([src.view(B, n_src, 3, H, W)], [tgt], ssim_rate) * S
+            idents = ops.photo_error_fwd([src.view(B, n_src, 3, H, W)], [tgt], ssim_rate, pad) * S
         loss, count, winners = ops.min_reproj_fwd(errs, valid, idents, weights, norm)
         if smooth is None:
             ctx.save_for_backward(K, count, hwc, tgt, *disps, *poses, *warped, *winners)
-            ctx.cfg = (S, n_src, ssim_rate, weights, norm, None)
+            ctx.cfg, ctx.conv = (S, n_src, ssim_rate, weights, norm, None), (pad, up)
             return loss[S]
         tgts = ops.pyramid(tgt, S)
         sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)
         ctx.save_for_backward(K, count, hwc, tgt, *disps, *poses, *warped, *winners, stats, *tgts[1:])
-        ctx.cfg = (S, n_src, ssim_rate, weights, norm, smooth)
+        ctx.cfg, ctx.conv = (S, n_src, ssim_rate, weights, norm, smooth), (pad, up)
         return loss[S] + sm_loss[S]
 
     @staticmethod
@@ -959,15 +968,17 @@ class _MinReprojLossFullRes(torch.autograd.Function):
         warped, winners = rest[:S], rest[S:2 * S]
         g_loss = _g_loss(S, g_total, None, count.device)
         g_errs = ops.min_reproj_bwd(winners, count, g_loss, n_src, weights, norm, [tuple(tgt.shape[2:])] * S)
-        d_warped = ops.photo_error_bwd(warped, [tgt] * S, ssim_rate, g_errs)
-        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", d_warped)
+        pad, up = ctx.conv
+        d_warped = ops.photo_error_bwd(warped, [tgt] * S, ssim_rate, g_errs, pad)
+        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", d_warped, upsample=up)
         if smooth is not None:      # the smoothness gradient is added in place by its kernel: no aten call
             ops.disp_smooth_bwd(disps, [tgt] + rest[2 * S + 1:], rest[2 * S], g_loss, *smooth, out=d_disps)
         return (None,) * 5 + tuple(d_disps) + tuple(d_poses)
 
 
 def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, *, ssim_rate, auto_mask=True, weights=None, norm="kept",
-                          smooth_weight=0.0, smooth_normalize=True, smooth_edge="mean_abs", full_res=False):
+                          smooth_weight=0.0, smooth_normalize=True, smooth_edge="mean_abs", full_res=False, ssim_padding="zero",
+                          upsample="align_corners"):
     """The Monodepth2-style loss of INTEGRATION.md ("Your own loss on the library's warp") in one call and ONE autograd node: per
     pixel the smallest ssim_rate * SSIM + (1 - ssim_rate) * L1 error over the warped sources that are in view, averaged per scale
     over the pixels where it is strictly below the error of every UNWARPED source (`auto_mask`; off: over the pixels some source
@@ -994,7 +1005,15 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
     alone, and pred_disps[s] may have any size unless smooth_weight > 0), `photometric_error` of the S full-resolution warped sets
     against the full-resolution target, the identity error computed once and handed to `min_reprojection` for every scale, and the
     smoothness term unchanged: each disparity at its own size on the target pyramid.  The total and the gradients are those of
-    these stages called one after the other, bit for bit.  With full_res=False (the default) the call is what it was."""
+    these stages called one after the other, bit for bit.  With full_res=False (the default) the call is what it was.
+
+    ssim_padding="reflect" and upsample="half_pixel" are Monodepth2's own conventions, the `padding` of `photometric_error` -- applied
+    to the warped error and to the identity error alike -- and the `upsample` of `warp_full_res`; the smoothness term looks at neither.
+    Still one node with the same launches, and still the stages called one after the other with these arguments, bit for bit.
+    upsample="half_pixel" without full_res=True raises ValueError (the pyramid form upsamples nothing), as does any unknown name."""
+    _lib.ssim_padding_id(ssim_padding, "ssim_padding")
+    if _lib.upsample_id(upsample) != _lib.UPSAMPLE_ALIGN_CORNERS and not full_res:
+        raise ValueError("upsample=%r needs full_res=True: the pyramid form compares every disparity at its own size" % (upsample,))
     if smooth_weight:       # (0, the default: nothing below is looked at, the call costs what it cost before the term existed)
         smooth_weight = float(smooth_weight)
         if not smooth_weight >= 0.0:
@@ -1020,7 +1039,7 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
     S = len(disps)
     weights = _scale_weights(weights, S)
     smooth = (tuple(smooth_weight * w for w in weights), bool(smooth_normalize), smooth_edge) if smooth_weight else None
-    cfg = (float(ssim_rate), bool(auto_mask), weights, norm, smooth)
+    cfg = (float(ssim_rate), bool(auto_mask), weights, norm, smooth, ssim_padding, upsample)
     _lib.min_reproj_norm_id(norm)
     return node.apply(tgt.detach(), src.detach().view(B, 3 * n_src, H, W), K, cfg, S, *disps, *poses)
 
