@@ -156,6 +156,20 @@ def upsample_id(name):
     return _setting(UPSAMPLES, "upsample", name)
 
 
+# include/sfmwarp_pose.h: what a pose holds, the inverse transform per source, and the affine map in front of depth = 1 / disp
+POSE_EULER, POSE_AXIS_ANGLE, POSE_MATRIX = 0, 1, 2
+POSE_FORMATS = {"euler": POSE_EULER, "axis_angle": POSE_AXIS_ANGLE, "matrix": POSE_MATRIX}
+
+
+def pose_format_id(name):
+    """SFM_POSE_* of a `pose_format` argument; anything outside the table is a ValueError"""
+    return _setting(POSE_FORMATS, "pose_format", name)
+
+
+class SfmPoseConv(C.Structure):
+    _fields_ = [("pose_format", C.c_int32), ("invert", C.c_int32 * SFM_MAX_SRC), ("disp_scale", C.c_float), ("disp_shift", C.c_float)]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -242,6 +256,19 @@ CONV_SYMBOLS = {
 }
 
 
+# every symbol declared in the side header include/sfmwarp_pose.h (to be folded into SYMBOLS together with that header)
+POSE_SYMBOLS = {
+    "sfm_pose_mat_fwd": (_I, [_FP, C.c_int32, C.c_int32, _FP, _I, _V]),
+    "sfm_pose_mat_bwd": (_I, [_FP, C.c_int32, C.c_int32, _FP, _FP, _I, _V]),
+    "sfm_warp_pyramid_conv_fwd": (_I, [C.POINTER(SfmWarpPyramidDesc), C.POINTER(SfmPoseConv), _V]),
+    "sfm_warp_pyramid_conv_bwd_workspace_bytes": (_Z, [C.POINTER(SfmWarpPyramidDesc), C.POINTER(SfmPoseConv)]),
+    "sfm_warp_pyramid_conv_bwd": (_I, [C.POINTER(SfmWarpPyramidDesc), C.POINTER(SfmPoseConv), _V, _Z, _V]),
+    "sfm_warp_full_res_conv_fwd": (_I, [C.POINTER(SfmWarpFullResDesc), C.c_int32, C.POINTER(SfmPoseConv), _V]),
+    "sfm_warp_full_res_conv_bwd_workspace_bytes": (_Z, [C.POINTER(SfmWarpFullResDesc), C.c_int32, C.POINTER(SfmPoseConv)]),
+    "sfm_warp_full_res_conv_bwd": (_I, [C.POINTER(SfmWarpFullResDesc), C.c_int32, C.POINTER(SfmPoseConv), _V, _Z, _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -253,7 +280,7 @@ def _load():
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SMOOTH_SYMBOLS.items()) \
-            + list(FULL_RES_SYMBOLS.items()) + list(CONV_SYMBOLS.items()):
+            + list(FULL_RES_SYMBOLS.items()) + list(CONV_SYMBOLS.items()) + list(POSE_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -144,19 +144,16 @@ __device__ __forceinline__ void inv3(const float* K, float* o) {
   o[8] = (a * e - b * d) / det;
 }
 
-// proj_tgt_to_src (models/transform.py:64-91) for one sample; rows 0..2 of K4 . [R|t]
-__device__ __forceinline__ void make_geom(const float* pose6, const float* K, Geom& g) {
+// P = K . T for T = rows 0..2 of the source-from-target transform (3x4, row-major: [R|t] of pose_vec2mat, or any 3x4), with
+// the inverse camera and M: rows 0..2 of K4 . T of proj_tgt_to_src (models/transform.py:86-88).  The ONE P = K . T step: make_geom
+// (sfm_pose.h) and every pose convention of include/sfmwarp_pose.h end here.
+__device__ __forceinline__ void geom_from_T(const float* T, const float* K, Geom& g) {
 #pragma clang fp contract(off)
-  Rot rot;
-  euler2mat(pose6, rot);
-  const float t[3] = {pose6[3], pose6[4], pose6[5]};
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
-      g.P[i * 4 + j] = K[i * 3 + 0] * rot.R[0 * 3 + j] + K[i * 3 + 1] * rot.R[1 * 3 + j] + K[i * 3 + 2] * rot.R[2 * 3 + j];
-    g.P[i * 4 + 3] = K[i * 3 + 0] * t[0] + K[i * 3 + 1] * t[1] + K[i * 3 + 2] * t[2];
-  }
+    for (int j = 0; j < 4; ++j)
+      g.P[i * 4 + j] = K[i * 3 + 0] * T[0 * 4 + j] + K[i * 3 + 1] * T[1 * 4 + j] + K[i * 3 + 2] * T[2 * 4 + j];
   inv3(K, g.Kinv);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -166,7 +163,7 @@ __device__ __forceinline__ void make_geom(const float* pose6, const float* K, Ge
   g.pad[0] = g.pad[1] = 0.f;
 }
 
-// Backward of proj_tgt_to_src for one sample.
+// Backward of proj_tgt_to_src for one sample: the Euler tail behind the gradient of [R|t].
 //   gT3 = (K^T . gPm[0:3, :]) accumulated by the caller over scales: 3x4, row-major
 //   rot = euler2mat(pose6): taken as an argument so that a caller can compute it while the sums behind gT3 are still in flight
 __device__ __forceinline__ void pose_backward(const float* pose6, const Rot& rot, const float* gT3, float* d_pose6) {
@@ -189,12 +186,6 @@ __device__ __forceinline__ void pose_backward(const float* pose6, const Rot& rot
     d_pose6[k] = (pose6[k] > -pi && pose6[k] < pi) ? g : 0.f;   // F.clip backward (transform.py:23)
     d_pose6[3 + k] = gT3[k * 4 + 3];
   }
-}
-
-__device__ __forceinline__ void pose_backward(const float* pose6, const float* gT3, float* d_pose6) {
-  Rot rot;
-  euler2mat(pose6, rot);
-  pose_backward(pose6, rot, gT3, d_pose6);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "sfm_common.h"
+#include "sfm_pose.h"
 #include "sfm_resize.h"
 #include "sfm_warp_pixel.h"
 
@@ -67,6 +68,28 @@ __global__ void pose_proj_bwd_kernel(const float* __restrict__ pose6, const floa
   pose_backward(pose6 + n * 6, gT3, d);
 #pragma unroll
   for (int k = 0; k < 6; ++k) d_pose6[n * 6 + k] = d[k];
+}
+
+// ------------------------------------------------------------------------------------------
+// pose -> [R|t] in a chosen convention (include/sfmwarp_pose.h): one thread per matrix; format and invert are uniform over the launch
+// ------------------------------------------------------------------------------------------
+__global__ void pose_mat_fwd_kernel(const float* __restrict__ pose6, const int format, const int invert, float* __restrict__ T, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float t[12];
+  pose_mat(format, invert, pose6 + (size_t)n * 6, t);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T[(size_t)n * 12 + k] = t[k];
+}
+
+__global__ void pose_mat_bwd_kernel(const float* __restrict__ pose6, const int format, const int invert, const float* __restrict__ g_T,
+                                    float* __restrict__ d_pose6, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float g[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) g[k] = g_T[(size_t)n * 12 + k];
+  pose_mat_backward_rt(format, invert, pose6 + (size_t)n * 6, g, d_pose6 + (size_t)n * 6);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1052,6 +1075,33 @@ int sfm_pose_proj_bwd(const float* pose6, const float* K, const float* g_proj, f
   SFM_REQUIRE(N >= 0, SFM_ERR_SHAPE, "sfm_pose_proj_bwd: N=%d", N);
   hipLaunchKernelGGL(pose_proj_bwd_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, pose6, K, g_proj, d_pose6, N);
   return check_launch("sfm_pose_proj_bwd");
+}
+
+// include/sfmwarp_pose.h: the pose operator
+static int check_pose_mat(const char* who, int32_t format, int32_t invert, int N) {
+  SFM_REQUIRE(format == SFM_POSE_EULER || format == SFM_POSE_AXIS_ANGLE, SFM_ERR_CONFIG, "%s: format=%d, need SFM_POSE_EULER or SFM_POSE_AXIS_ANGLE", who,
+              (int)format);
+  SFM_REQUIRE(invert == 0 || invert == 1, SFM_ERR_CONFIG, "%s: invert=%d, need 0 or 1", who, (int)invert);
+  SFM_REQUIRE(N >= 0, SFM_ERR_SHAPE, "%s: N=%d", who, N);
+  return SFM_OK;
+}
+
+int sfm_pose_mat_fwd(const float* pose6, int32_t format, int32_t invert, float* T, int N, void* stream) {
+  const char* who = "sfm_pose_mat_fwd";
+  if (int e = check_pose_mat(who, format, invert, N)) return e;
+  if (N == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
+  SFM_REQUIRE(pose6 && T, SFM_ERR_NULL, "%s: NULL pointer", who);
+  hipLaunchKernelGGL(pose_mat_fwd_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, pose6, (int)format, (int)invert, T, N);
+  return check_launch(who);
+}
+
+int sfm_pose_mat_bwd(const float* pose6, int32_t format, int32_t invert, const float* g_T, float* d_pose6, int N, void* stream) {
+  const char* who = "sfm_pose_mat_bwd";
+  if (int e = check_pose_mat(who, format, invert, N)) return e;
+  if (N == 0) return SFM_OK;
+  SFM_REQUIRE(pose6 && g_T && d_pose6, SFM_ERR_NULL, "%s: NULL pointer", who);
+  hipLaunchKernelGGL(pose_mat_bwd_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, pose6, (int)format, (int)invert, g_T, d_pose6, N);
+  return check_launch(who);
 }
 
 static int check_warp_shape(const char* who, int N, int C, int H, int W) {

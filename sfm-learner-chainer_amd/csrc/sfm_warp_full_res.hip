@@ -12,6 +12,7 @@
 // weights are the half-pixel ones of F.interpolate(align_corners=False) (sfm_resize.h), everything else is the same code; the
 // align-corners instantiations keep theirs.
 #include "sfm_common.h"
+#include "sfm_pose.h"
 #include "sfm_resize.h"
 #include "sfm_warp_pixel.h"
 #include "../../include/sfmwarp_full_res.h"
@@ -44,6 +45,7 @@ struct WarpFullArgs {
   bool resampled[SFM_MAX_SCALES];
   int H, W, nblk;                         // nblk: 256-pixel blocks of one image
   int B, n_src, n_scales;
+  PoseConvArgs conv;                      // include/sfmwarp_pose.h: read by the _conv_ kernels only
 };
 
 // where a block works: scale, sample, block of the image -- uniform over the block
@@ -67,9 +69,14 @@ __device__ __forceinline__ auto warp_full_image(const float* src, const size_t i
   else return PlanarImage{src + image * 3 * (size_t)P, (size_t)P};
 }
 
-// the geometry of every source of this block's sample: lane i builds source i
+// the geometry of every source of this block's sample: lane i builds source i.  CONV: under the conventions of
+// include/sfmwarp_pose.h -- the format is tested here, once per block, by the lanes that build
+template <bool CONV>
 __device__ __forceinline__ void warp_full_geoms(const WarpFullArgs& A, const WarpFullBlock& w, Geom* g) {
-  if ((int)threadIdx.x < A.n_src) make_geom(A.pose[threadIdx.x] + (size_t)w.b * 6, A.K + (size_t)w.b * 9, g[threadIdx.x]);
+  if ((int)threadIdx.x < A.n_src) {
+    if constexpr (CONV) make_geom_conv(A.conv, threadIdx.x, A.pose[threadIdx.x], (size_t)w.b, A.K + (size_t)w.b * 9, g[threadIdx.x]);
+    else make_geom(A.pose[threadIdx.x] + (size_t)w.b * 6, A.K + (size_t)w.b * 9, g[threadIdx.x]);
+  }
   __syncthreads();
 }
 
@@ -91,17 +98,20 @@ __device__ __forceinline__ float warp_full_disp(const WarpFullArgs& A, const War
   return resize_read(resize_taps(u, v, h, ww), disp, ww);
 }
 
-template <bool HWC, bool HP = false>
-__global__ void __launch_bounds__(WF_BLOCK) warp_full_fwd_kernel(const WarpFullArgs A) {
+// CONV = false is the kernel as it stood; CONV = true differs in the geometry lanes and in how up[s] becomes a depth
+template <bool HWC, bool HP, bool CONV>
+__device__ __forceinline__ void warp_full_fwd_body(const WarpFullArgs& A) {
 #pragma clang fp contract(off)
   __shared__ Geom g[SFM_MAX_SRC];
   const WarpFullBlock w = warp_full_block(A);
-  warp_full_geoms(A, w, g);
+  warp_full_geoms<CONV>(A, w, g);
   const int H = A.H, W = A.W, P = H * W;
   const int j = w.blk * WF_BLOCK + threadIdx.x;
   if (j >= P) return;
   const int y = j / W, x = j - y * W;
-  const float depth = 1.0f / warp_full_disp<HP>(A, w, y, x, j);      // models/base_model.py:60
+  float disp = warp_full_disp<HP>(A, w, y, x, j);
+  if constexpr (CONV) disp = conv_sd(A.conv, disp);
+  const float depth = 1.0f / disp;                                     // models/base_model.py:60
   const float D[3] = {depth, depth, depth};
   float* valid = A.valid[w.s];
   for (int i = 0; i < A.n_src; ++i) {
@@ -121,18 +131,28 @@ __global__ void __launch_bounds__(WF_BLOCK) warp_full_fwd_kernel(const WarpFullA
 }
 
 template <bool HWC, bool HP = false>
-__global__ void __launch_bounds__(WF_BLOCK) warp_full_bwd_kernel(const WarpFullArgs A) {
+__global__ void __launch_bounds__(WF_BLOCK) warp_full_fwd_kernel(const WarpFullArgs A) {
+  warp_full_fwd_body<HWC, HP, false>(A);
+}
+template <bool HWC, bool HP = false>
+__global__ void __launch_bounds__(WF_BLOCK) warp_full_conv_fwd_kernel(const WarpFullArgs A) {
+  warp_full_fwd_body<HWC, HP, true>(A);
+}
+
+template <bool HWC, bool HP, bool CONV>
+__device__ __forceinline__ void warp_full_bwd_body(const WarpFullArgs& A) {
 #pragma clang fp contract(off)
   __shared__ Geom g[SFM_MAX_SRC];
   __shared__ float red[WF_WAVES][SFM_MAX_SRC][12];
   const WarpFullBlock w = warp_full_block(A);
-  warp_full_geoms(A, w, g);
+  warp_full_geoms<CONV>(A, w, g);
   const int H = A.H, W = A.W, P = H * W;
   const int j = w.blk * WF_BLOCK + threadIdx.x;
   const bool have = j < P;                       // no early exit: the lanes of a wave add up their sums below
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int y = j / W, x = j - y * W;
-  const float disp = have ? warp_full_disp<HP>(A, w, y, x, j) : 1.0f;
+  float disp = have ? warp_full_disp<HP>(A, w, y, x, j) : 1.0f;
+  if constexpr (CONV) disp = have ? conv_sd(A.conv, disp) : 1.0f;      // (sd from here on)
   const float depth = 1.0f / disp;               // models/base_model.py:60
   const float D[3] = {depth, depth, depth};
   float g_depth = 0.f;
@@ -155,7 +175,11 @@ __global__ void __launch_bounds__(WF_BLOCK) warp_full_bwd_kernel(const WarpFullA
       for (int k = 0; k < 12; ++k) red[wave][i][k] = acc[k];
     }
   }
-  if (have) A.d_up[w.s][(size_t)w.b * P + j] = -g_depth / (disp * disp);      // depth = 1 / up
+  if constexpr (CONV) {
+    if (have) A.d_up[w.s][(size_t)w.b * P + j] = conv_d_disp(A.conv, g_depth, disp);      // the factor disp_scale before the gather
+  } else {
+    if (have) A.d_up[w.s][(size_t)w.b * P + j] = -g_depth / (disp * disp);      // depth = 1 / up
+  }
   __syncthreads();
   if ((int)threadIdx.x < A.n_src * 12) {
     const int i = threadIdx.x / 12, k = threadIdx.x - i * 12;
@@ -164,6 +188,15 @@ __global__ void __launch_bounds__(WF_BLOCK) warp_full_bwd_kernel(const WarpFullA
     for (int v = 0; v < WF_WAVES; ++v) s += red[v][i][k];
     A.part[((size_t)blockIdx.x * A.n_src + i) * 12 + k] = s;
   }
+}
+
+template <bool HWC, bool HP = false>
+__global__ void __launch_bounds__(WF_BLOCK) warp_full_bwd_kernel(const WarpFullArgs A) {
+  warp_full_bwd_body<HWC, HP, false>(A);
+}
+template <bool HWC, bool HP = false>
+__global__ void __launch_bounds__(WF_BLOCK) warp_full_conv_bwd_kernel(const WarpFullArgs A) {
+  warp_full_bwd_body<HWC, HP, true>(A);
 }
 
 // d_disp[s] = R_s^T d_up[s] for every resampled scale in one launch: resize_bwd_kernel with one term, one thread per element of
@@ -216,7 +249,8 @@ __global__ void __launch_bounds__(256) warp_full_gather_kernel(const WarpFullArg
 }
 
 // one wave per (sample, source): warp_pyr_fold_kernel with one camera for every scale
-__global__ void __launch_bounds__(64) warp_full_fold_kernel(const WarpFullArgs A) {
+template <bool CONV>
+__device__ __forceinline__ void warp_full_fold_body(const WarpFullArgs& A) {
   const int b = blockIdx.x / A.n_src, i = blockIdx.x - b * A.n_src, lane = threadIdx.x;
   const int nblk = A.nblk;
   float gT3[12];
@@ -234,15 +268,24 @@ __global__ void __launch_bounds__(64) warp_full_fold_kernel(const WarpFullArgs A
     kt_times_gpm(A.K + (size_t)b * 9, gPm, gT3, s > 0);
   }
   if (lane == 0) {
-    float d[6];
-    pose_backward(A.pose[i] + (size_t)b * 6, gT3, d);
+    if constexpr (CONV) {
+      pose_fold_conv(A.conv, i, A.pose[i], (size_t)b, gT3, A.d_pose[i]);
+    } else {
+      float d[6];
+      pose_backward(A.pose[i] + (size_t)b * 6, gT3, d);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) A.d_pose[i][(size_t)b * 6 + k] = d[k];
+      for (int k = 0; k < 6; ++k) A.d_pose[i][(size_t)b * 6 + k] = d[k];
+    }
   }
 }
 
+__global__ void __launch_bounds__(64) warp_full_fold_kernel(const WarpFullArgs A) { warp_full_fold_body<false>(A); }
+__global__ void __launch_bounds__(64) warp_full_conv_fold_kernel(const WarpFullArgs A) { warp_full_fold_body<true>(A); }
+
 // The sizes and the layout, in the order the header states them: everything the workspace query needs, no pointer looked at.
-static int warp_full_shape(WarpFullArgs& A, const char* who, const SfmWarpFullResDesc* d, const int32_t upsample = SFM_UPSAMPLE_ALIGN_CORNERS) {
+// conv: the call is one of include/sfmwarp_pose.h and `c` its conventions, checked last.
+static int warp_full_shape(WarpFullArgs& A, const char* who, const SfmWarpFullResDesc* d, const int32_t upsample = SFM_UPSAMPLE_ALIGN_CORNERS,
+                           const bool conv = false, const SfmPoseConv* c = nullptr) {
   SFM_REQUIRE(d, SFM_ERR_NULL, "%s: NULL descriptor", who);
   SFM_REQUIRE(d->n_src >= 1 && d->n_src <= SFM_MAX_SRC, SFM_ERR_SHAPE, "%s: n_src=%d, need 1..%d", who, d->n_src, SFM_MAX_SRC);
   SFM_REQUIRE(d->n_scales >= 1 && d->n_scales <= SFM_MAX_SCALES, SFM_ERR_SHAPE, "%s: n_scales=%d, need 1..%d", who, d->n_scales,
@@ -275,6 +318,7 @@ static int warp_full_shape(WarpFullArgs& A, const char* who, const SfmWarpFullRe
               d->image_layout);
   SFM_REQUIRE(upsample == SFM_UPSAMPLE_ALIGN_CORNERS || upsample == SFM_UPSAMPLE_HALF_PIXEL, SFM_ERR_CONFIG, "%s: upsample=%d", who,
               (int)upsample);
+  if (conv) return check_pose_conv(who, c, d->n_src, A.conv);
   return SFM_OK;
 }
 
@@ -311,16 +355,26 @@ static size_t warp_full_ws_bytes(const WarpFullArgs& A) {
   return need ? (need + 255) / 256 * 256 : 256;
 }
 
-// the three calls, for either upsampling: the existing entry points pass SFM_UPSAMPLE_ALIGN_CORNERS
-static int warp_full_fwd(const char* who, const SfmWarpFullResDesc* d, const int32_t upsample, void* stream) {
+// the three calls, for either upsampling: the existing entry points pass SFM_UPSAMPLE_ALIGN_CORNERS.  conv: a call of
+// include/sfmwarp_pose.h; conventions that are the defaults launch the existing kernels
+static int warp_full_fwd(const char* who, const SfmWarpFullResDesc* d, const int32_t upsample, void* stream, const bool conv = false,
+                         const SfmPoseConv* c = nullptr) {
   WarpFullArgs A;
-  if (int e = warp_full_shape(A, who, d, upsample)) return e;
+  if (int e = warp_full_shape(A, who, d, upsample, conv, c)) return e;
   if (d->B == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
   if (int e = warp_full_pointers(A, who, d, false)) return e;
   const dim3 grid(A.n_scales * A.B * A.nblk);
   const hipStream_t st = (hipStream_t)stream;
   const bool hwc = d->image_layout == SFM_LAYOUT_HWC;
-  if (upsample == SFM_UPSAMPLE_HALF_PIXEL) {
+  if (conv && !pose_conv_is_default(A.conv)) {
+    if (upsample == SFM_UPSAMPLE_HALF_PIXEL) {
+      if (hwc) hipLaunchKernelGGL((warp_full_conv_fwd_kernel<true, true>), grid, dim3(WF_BLOCK), 0, st, A);
+      else hipLaunchKernelGGL((warp_full_conv_fwd_kernel<false, true>), grid, dim3(WF_BLOCK), 0, st, A);
+    } else {
+      if (hwc) hipLaunchKernelGGL((warp_full_conv_fwd_kernel<true, false>), grid, dim3(WF_BLOCK), 0, st, A);
+      else hipLaunchKernelGGL((warp_full_conv_fwd_kernel<false, false>), grid, dim3(WF_BLOCK), 0, st, A);
+    }
+  } else if (upsample == SFM_UPSAMPLE_HALF_PIXEL) {
     if (hwc) hipLaunchKernelGGL((warp_full_fwd_kernel<true, true>), grid, dim3(WF_BLOCK), 0, st, A);
     else hipLaunchKernelGGL((warp_full_fwd_kernel<false, true>), grid, dim3(WF_BLOCK), 0, st, A);
   } else {
@@ -330,9 +384,10 @@ static int warp_full_fwd(const char* who, const SfmWarpFullResDesc* d, const int
   return check_launch(who);
 }
 
-static int warp_full_bwd(const char* who, const SfmWarpFullResDesc* d, const int32_t upsample, void* ws, size_t ws_bytes, void* stream) {
+static int warp_full_bwd(const char* who, const SfmWarpFullResDesc* d, const int32_t upsample, void* ws, size_t ws_bytes, void* stream,
+                         const bool conv = false, const SfmPoseConv* c = nullptr) {
   WarpFullArgs A;
-  if (int e = warp_full_shape(A, who, d, upsample)) return e;
+  if (int e = warp_full_shape(A, who, d, upsample, conv, c)) return e;
   if (d->B == 0) return SFM_OK;
   if (int e = warp_full_pointers(A, who, d, true)) return e;
   const size_t need = warp_full_ws_bytes(A);
@@ -345,7 +400,16 @@ static int warp_full_bwd(const char* who, const SfmWarpFullResDesc* d, const int
   const dim3 grid(A.n_scales * A.B * A.nblk);
   const hipStream_t st = (hipStream_t)stream;
   const bool hwc = d->image_layout == SFM_LAYOUT_HWC, hp = upsample == SFM_UPSAMPLE_HALF_PIXEL;
-  if (hp) {
+  const bool other = conv && !pose_conv_is_default(A.conv);
+  if (other) {
+    if (hp) {
+      if (hwc) hipLaunchKernelGGL((warp_full_conv_bwd_kernel<true, true>), grid, dim3(WF_BLOCK), 0, st, A);
+      else hipLaunchKernelGGL((warp_full_conv_bwd_kernel<false, true>), grid, dim3(WF_BLOCK), 0, st, A);
+    } else {
+      if (hwc) hipLaunchKernelGGL((warp_full_conv_bwd_kernel<true, false>), grid, dim3(WF_BLOCK), 0, st, A);
+      else hipLaunchKernelGGL((warp_full_conv_bwd_kernel<false, false>), grid, dim3(WF_BLOCK), 0, st, A);
+    }
+  } else if (hp) {
     if (hwc) hipLaunchKernelGGL((warp_full_bwd_kernel<true, true>), grid, dim3(WF_BLOCK), 0, st, A);
     else hipLaunchKernelGGL((warp_full_bwd_kernel<false, true>), grid, dim3(WF_BLOCK), 0, st, A);
   } else {
@@ -358,7 +422,8 @@ static int warp_full_bwd(const char* who, const SfmWarpFullResDesc* d, const int
     if (hp) hipLaunchKernelGGL(warp_full_gather_kernel<true>, gg, dim3(256), 0, st, A);
     else hipLaunchKernelGGL(warp_full_gather_kernel<false>, gg, dim3(256), 0, st, A);
   }
-  hipLaunchKernelGGL(warp_full_fold_kernel, dim3(d->B * d->n_src), dim3(64), 0, st, A);
+  if (other) hipLaunchKernelGGL(warp_full_conv_fold_kernel, dim3(d->B * d->n_src), dim3(64), 0, st, A);
+  else hipLaunchKernelGGL(warp_full_fold_kernel, dim3(d->B * d->n_src), dim3(64), 0, st, A);
   return check_launch(who);
 }
 
@@ -395,6 +460,21 @@ size_t sfm_warp_full_res_up_bwd_workspace_bytes(const SfmWarpFullResDesc* d, int
 
 int sfm_warp_full_res_up_bwd(const SfmWarpFullResDesc* d, int32_t upsample, void* ws, size_t ws_bytes, void* stream) {
   return warp_full_bwd("sfm_warp_full_res_up_bwd", d, upsample, ws, ws_bytes, stream);
+}
+
+// include/sfmwarp_pose.h
+int sfm_warp_full_res_conv_fwd(const SfmWarpFullResDesc* d, int32_t upsample, const SfmPoseConv* c, void* stream) {
+  return warp_full_fwd("sfm_warp_full_res_conv_fwd", d, upsample, stream, true, c);
+}
+
+size_t sfm_warp_full_res_conv_bwd_workspace_bytes(const SfmWarpFullResDesc* d, int32_t upsample, const SfmPoseConv* c) {
+  WarpFullArgs A;
+  if (warp_full_shape(A, "sfm_warp_full_res_conv_bwd_workspace_bytes", d, upsample, true, c)) return 0;
+  return warp_full_ws_bytes(A);
+}
+
+int sfm_warp_full_res_conv_bwd(const SfmWarpFullResDesc* d, int32_t upsample, const SfmPoseConv* c, void* ws, size_t ws_bytes, void* stream) {
+  return warp_full_bwd("sfm_warp_full_res_conv_bwd", d, upsample, ws, ws_bytes, stream, true, c);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 // builds the geometry of each of its sources once (one LDS slot per source, built by n_src lanes side by side); a thread reads
 // its disparity once and loops over the sources.
 #include "sfm_common.h"
+#include "sfm_pose.h"
 #include "sfm_warp_pixel.h"
 
 namespace sfm {
@@ -29,6 +30,7 @@ struct WarpPyrArgs {
   int nblk[SFM_MAX_SCALES];               // 256-pixel blocks of one image of scale s
   int begin[SFM_MAX_SCALES + 1];          // prefix sums of B * nblk[s]: the first block of scale s
   int B, n_src, n_scales;
+  PoseConvArgs conv;                      // include/sfmwarp_pose.h: read by the _conv_ kernels only
 };
 
 // where a block works: scale, sample, block of the image -- uniform over the block
@@ -53,23 +55,32 @@ __device__ __forceinline__ auto warp_pyr_image(const float* src, const size_t im
   else return PlanarImage{src + image * 3 * (size_t)P, (size_t)P};
 }
 
-// the geometry of every source of this block's (sample, scale): lane i builds source i
+// the geometry of every source of this block's (sample, scale): lane i builds source i.  CONV: under the conventions of
+// include/sfmwarp_pose.h -- the format is tested here, once per block, by the lanes that build
+template <bool CONV>
 __device__ __forceinline__ void warp_pyr_geoms(const WarpPyrArgs& A, const WarpPyrBlock& w, Geom* g) {
-  if ((int)threadIdx.x < A.n_src) make_geom(A.pose[threadIdx.x] + (size_t)w.b * 6, A.K + ((size_t)w.b * A.n_scales + w.s) * 9, g[threadIdx.x]);
+  if ((int)threadIdx.x < A.n_src) {
+    const float* K = A.K + ((size_t)w.b * A.n_scales + w.s) * 9;
+    if constexpr (CONV) make_geom_conv(A.conv, threadIdx.x, A.pose[threadIdx.x], (size_t)w.b, K, g[threadIdx.x]);
+    else make_geom(A.pose[threadIdx.x] + (size_t)w.b * 6, K, g[threadIdx.x]);
+  }
   __syncthreads();
 }
 
-template <bool HWC>
-__global__ void __launch_bounds__(WP_BLOCK) warp_pyr_fwd_kernel(const WarpPyrArgs A) {
+// CONV = false is the kernel as it stood; CONV = true differs in the geometry lanes and in how the disparity becomes a depth
+template <bool HWC, bool CONV>
+__device__ __forceinline__ void warp_pyr_fwd_body(const WarpPyrArgs& A) {
 #pragma clang fp contract(off)
   __shared__ Geom g[SFM_MAX_SRC];
   const WarpPyrBlock w = warp_pyr_block(A);
-  warp_pyr_geoms(A, w, g);
+  warp_pyr_geoms<CONV>(A, w, g);
   const int H = A.H[w.s], W = A.W[w.s], P = H * W;
   const int j = w.blk * WP_BLOCK + threadIdx.x;
   if (j >= P) return;
   const int y = j / W, x = j - y * W;
-  const float depth = 1.0f / A.disp[w.s][(size_t)w.b * P + j];      // models/base_model.py:60
+  float disp = A.disp[w.s][(size_t)w.b * P + j];
+  if constexpr (CONV) disp = conv_sd(A.conv, disp);
+  const float depth = 1.0f / disp;                                    // models/base_model.py:60
   const float D[3] = {depth, depth, depth};
   float* valid = A.valid[w.s];
   for (int i = 0; i < A.n_src; ++i) {
@@ -89,17 +100,27 @@ __global__ void __launch_bounds__(WP_BLOCK) warp_pyr_fwd_kernel(const WarpPyrArg
 }
 
 template <bool HWC>
-__global__ void __launch_bounds__(WP_BLOCK) warp_pyr_bwd_kernel(const WarpPyrArgs A) {
+__global__ void __launch_bounds__(WP_BLOCK) warp_pyr_fwd_kernel(const WarpPyrArgs A) {
+  warp_pyr_fwd_body<HWC, false>(A);
+}
+template <bool HWC>
+__global__ void __launch_bounds__(WP_BLOCK) warp_pyr_conv_fwd_kernel(const WarpPyrArgs A) {
+  warp_pyr_fwd_body<HWC, true>(A);
+}
+
+template <bool HWC, bool CONV>
+__device__ __forceinline__ void warp_pyr_bwd_body(const WarpPyrArgs& A) {
 #pragma clang fp contract(off)
   __shared__ Geom g[SFM_MAX_SRC];
   __shared__ float red[WP_WAVES][SFM_MAX_SRC][12];
   const WarpPyrBlock w = warp_pyr_block(A);
-  warp_pyr_geoms(A, w, g);
+  warp_pyr_geoms<CONV>(A, w, g);
   const int H = A.H[w.s], W = A.W[w.s], P = H * W;
   const int j = w.blk * WP_BLOCK + threadIdx.x;
   const bool have = j < P;                       // no early exit: the lanes of a wave add up their sums below
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float disp = have ? A.disp[w.s][(size_t)w.b * P + j] : 1.0f;
+  float disp = have ? A.disp[w.s][(size_t)w.b * P + j] : 1.0f;
+  if constexpr (CONV) disp = have ? conv_sd(A.conv, disp) : 1.0f;      // (sd from here on)
   const float depth = 1.0f / disp;               // models/base_model.py:60
   const float D[3] = {depth, depth, depth};
   float g_depth = 0.f;
@@ -122,7 +143,11 @@ __global__ void __launch_bounds__(WP_BLOCK) warp_pyr_bwd_kernel(const WarpPyrArg
       for (int k = 0; k < 12; ++k) red[wave][i][k] = acc[k];
     }
   }
-  if (have) A.d_disp[w.s][(size_t)w.b * P + j] = -g_depth / (disp * disp);      // depth = 1 / disp
+  if constexpr (CONV) {
+    if (have) A.d_disp[w.s][(size_t)w.b * P + j] = conv_d_disp(A.conv, g_depth, disp);
+  } else {
+    if (have) A.d_disp[w.s][(size_t)w.b * P + j] = -g_depth / (disp * disp);      // depth = 1 / disp
+  }
   __syncthreads();
   if ((int)threadIdx.x < A.n_src * 12) {
     const int i = threadIdx.x / 12, k = threadIdx.x - i * 12;
@@ -133,9 +158,19 @@ __global__ void __launch_bounds__(WP_BLOCK) warp_pyr_bwd_kernel(const WarpPyrArg
   }
 }
 
+template <bool HWC>
+__global__ void __launch_bounds__(WP_BLOCK) warp_pyr_bwd_kernel(const WarpPyrArgs A) {
+  warp_pyr_bwd_body<HWC, false>(A);
+}
+template <bool HWC>
+__global__ void __launch_bounds__(WP_BLOCK) warp_pyr_conv_bwd_kernel(const WarpPyrArgs A) {
+  warp_pyr_bwd_body<HWC, true>(A);
+}
+
 // one wave per (sample, source): per scale the fixed-order sum of that scale's block partials in fp64, rounded to fp32 and taken
-// through that scale's K^T; the scales added in ascending order; then the pose backward
-__global__ void __launch_bounds__(64) warp_pyr_fold_kernel(const WarpPyrArgs A) {
+// through that scale's K^T; the scales added in ascending order; then the pose backward (CONV: of the chosen convention)
+template <bool CONV>
+__device__ __forceinline__ void warp_pyr_fold_body(const WarpPyrArgs& A) {
   const int b = blockIdx.x / A.n_src, i = blockIdx.x - b * A.n_src, lane = threadIdx.x;
   float gT3[12];
   for (int s = 0; s < A.n_scales; ++s) {
@@ -153,15 +188,25 @@ __global__ void __launch_bounds__(64) warp_pyr_fold_kernel(const WarpPyrArgs A) 
     kt_times_gpm(A.K + ((size_t)b * A.n_scales + s) * 9, gPm, gT3, s > 0);
   }
   if (lane == 0) {
-    float d[6];
-    pose_backward(A.pose[i] + (size_t)b * 6, gT3, d);
+    if constexpr (CONV) {
+      pose_fold_conv(A.conv, i, A.pose[i], (size_t)b, gT3, A.d_pose[i]);
+    } else {
+      float d[6];
+      pose_backward(A.pose[i] + (size_t)b * 6, gT3, d);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) A.d_pose[i][(size_t)b * 6 + k] = d[k];
+      for (int k = 0; k < 6; ++k) A.d_pose[i][(size_t)b * 6 + k] = d[k];
+    }
   }
 }
 
+__global__ void __launch_bounds__(64) warp_pyr_fold_kernel(const WarpPyrArgs A) { warp_pyr_fold_body<false>(A); }
+__global__ void __launch_bounds__(64) warp_pyr_conv_fold_kernel(const WarpPyrArgs A) { warp_pyr_fold_body<true>(A); }
+
 // What both calls check and fill in, in the order the header states.  bwd: the pointers of the backward, else those of the forward.
-static int warp_pyr_setup(WarpPyrArgs& A, const char* who, const SfmWarpPyramidDesc* d, const bool bwd) {
+// conv: the call is one of include/sfmwarp_pose.h and `c` its conventions, checked between the layout and the empty batch;
+// sizes_only: its workspace query, which looks at no pointer.
+static int warp_pyr_setup(WarpPyrArgs& A, const char* who, const SfmWarpPyramidDesc* d, const bool bwd, const bool conv = false,
+                          const SfmPoseConv* c = nullptr, const bool sizes_only = false) {
   SFM_REQUIRE(d, SFM_ERR_NULL, "%s: NULL descriptor", who);
   const auto blocks = [&A](const int s, const int H, const int W) { return (long long)(A.nblk[s] = (H * W + WP_BLOCK - 1) / WP_BLOCK); };
   if (int e = check_pyramid_shape(who, d->B, d->n_src, "n_src", d->n_scales, d->H, d->W, "256-pixel blocks", "", blocks, A.H, A.W, A.begin))
@@ -169,6 +214,10 @@ static int warp_pyr_setup(WarpPyrArgs& A, const char* who, const SfmWarpPyramidD
   A.B = d->B, A.n_src = d->n_src, A.n_scales = d->n_scales;
   SFM_REQUIRE(d->image_layout == SFM_LAYOUT_PLANAR || d->image_layout == SFM_LAYOUT_HWC, SFM_ERR_CONFIG, "%s: image_layout=%d", who,
               d->image_layout);
+  if (conv) {
+    if (int e = check_pose_conv(who, c, d->n_src, A.conv)) return e;
+  }
+  if (sizes_only) return SFM_OK;
   if (d->B == 0) return SFM_OK;   // empty batch: nothing to do, pointers may be NULL
   SFM_REQUIRE(d->intrinsics, SFM_ERR_NULL, "%s: intrinsics is NULL", who);
   A.K = d->intrinsics;
@@ -198,6 +247,39 @@ static size_t warp_pyr_ws_bytes(const WarpPyrArgs& A) {
   return need ? (need + 255) / 256 * 256 : 256;
 }
 
+// the launches of a checked call; conv: the kernels that read A.conv, else the existing ones
+static int warp_pyr_launch_fwd(const char* who, const WarpPyrArgs& A, const bool hwc, const bool conv, void* stream) {
+  const dim3 grid(A.begin[A.n_scales]);
+  const hipStream_t st = (hipStream_t)stream;
+  if (conv) {
+    if (hwc) hipLaunchKernelGGL(warp_pyr_conv_fwd_kernel<true>, grid, dim3(WP_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL(warp_pyr_conv_fwd_kernel<false>, grid, dim3(WP_BLOCK), 0, st, A);
+  } else {
+    if (hwc) hipLaunchKernelGGL(warp_pyr_fwd_kernel<true>, grid, dim3(WP_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL(warp_pyr_fwd_kernel<false>, grid, dim3(WP_BLOCK), 0, st, A);
+  }
+  return check_launch(who);
+}
+
+static int warp_pyr_launch_bwd(const char* who, WarpPyrArgs& A, const bool hwc, const bool conv, void* ws, size_t ws_bytes, void* stream) {
+  const size_t need = warp_pyr_ws_bytes(A);
+  SFM_REQUIRE(ws && ws_bytes >= need, SFM_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, got %zu", who, need, ws ? ws_bytes : (size_t)0);
+  SFM_REQUIRE(((uintptr_t)ws & 255) == 0, SFM_ERR_WORKSPACE, "%s: workspace must be aligned to 256 bytes", who);
+  A.part = (float*)ws;
+  const dim3 grid(A.begin[A.n_scales]), fold(A.B * A.n_src);
+  const hipStream_t st = (hipStream_t)stream;
+  if (conv) {
+    if (hwc) hipLaunchKernelGGL(warp_pyr_conv_bwd_kernel<true>, grid, dim3(WP_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL(warp_pyr_conv_bwd_kernel<false>, grid, dim3(WP_BLOCK), 0, st, A);
+    hipLaunchKernelGGL(warp_pyr_conv_fold_kernel, fold, dim3(64), 0, st, A);
+  } else {
+    if (hwc) hipLaunchKernelGGL(warp_pyr_bwd_kernel<true>, grid, dim3(WP_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL(warp_pyr_bwd_kernel<false>, grid, dim3(WP_BLOCK), 0, st, A);
+    hipLaunchKernelGGL(warp_pyr_fold_kernel, fold, dim3(64), 0, st, A);
+  }
+  return check_launch(who);
+}
+
 }  // namespace sfm
 
 using namespace sfm;
@@ -209,10 +291,7 @@ int sfm_warp_pyramid_fwd(const SfmWarpPyramidDesc* d, void* stream) {
   WarpPyrArgs A;
   if (int e = warp_pyr_setup(A, who, d, false)) return e;
   if (d->B == 0) return SFM_OK;
-  const dim3 grid(A.begin[A.n_scales]);
-  if (d->image_layout == SFM_LAYOUT_HWC) hipLaunchKernelGGL(warp_pyr_fwd_kernel<true>, grid, dim3(WP_BLOCK), 0, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL(warp_pyr_fwd_kernel<false>, grid, dim3(WP_BLOCK), 0, (hipStream_t)stream, A);
-  return check_launch(who);
+  return warp_pyr_launch_fwd(who, A, d->image_layout == SFM_LAYOUT_HWC, false, stream);
 }
 
 size_t sfm_warp_pyramid_bwd_workspace_bytes(const SfmWarpPyramidDesc* d) {
@@ -226,16 +305,30 @@ int sfm_warp_pyramid_bwd(const SfmWarpPyramidDesc* d, void* ws, size_t ws_bytes,
   WarpPyrArgs A;
   if (int e = warp_pyr_setup(A, who, d, true)) return e;
   if (d->B == 0) return SFM_OK;
-  const size_t need = warp_pyr_ws_bytes(A);
-  SFM_REQUIRE(ws && ws_bytes >= need, SFM_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, got %zu", who, need, ws ? ws_bytes : (size_t)0);
-  SFM_REQUIRE(((uintptr_t)ws & 255) == 0, SFM_ERR_WORKSPACE, "%s: workspace must be aligned to 256 bytes", who);
-  A.part = (float*)ws;
-  const dim3 grid(A.begin[A.n_scales]);
-  const hipStream_t st = (hipStream_t)stream;
-  if (d->image_layout == SFM_LAYOUT_HWC) hipLaunchKernelGGL(warp_pyr_bwd_kernel<true>, grid, dim3(WP_BLOCK), 0, st, A);
-  else hipLaunchKernelGGL(warp_pyr_bwd_kernel<false>, grid, dim3(WP_BLOCK), 0, st, A);
-  hipLaunchKernelGGL(warp_pyr_fold_kernel, dim3(d->B * d->n_src), dim3(64), 0, st, A);
-  return check_launch(who);
+  return warp_pyr_launch_bwd(who, A, d->image_layout == SFM_LAYOUT_HWC, false, ws, ws_bytes, stream);
+}
+
+// include/sfmwarp_pose.h.  Conventions that are the defaults launch the existing kernels.
+int sfm_warp_pyramid_conv_fwd(const SfmWarpPyramidDesc* d, const SfmPoseConv* c, void* stream) {
+  const char* who = "sfm_warp_pyramid_conv_fwd";
+  WarpPyrArgs A;
+  if (int e = warp_pyr_setup(A, who, d, false, true, c)) return e;
+  if (d->B == 0) return SFM_OK;
+  return warp_pyr_launch_fwd(who, A, d->image_layout == SFM_LAYOUT_HWC, !pose_conv_is_default(A.conv), stream);
+}
+
+size_t sfm_warp_pyramid_conv_bwd_workspace_bytes(const SfmWarpPyramidDesc* d, const SfmPoseConv* c) {
+  WarpPyrArgs A;
+  if (warp_pyr_setup(A, "sfm_warp_pyramid_conv_bwd_workspace_bytes", d, true, true, c, true)) return 0;
+  return warp_pyr_ws_bytes(A);
+}
+
+int sfm_warp_pyramid_conv_bwd(const SfmWarpPyramidDesc* d, const SfmPoseConv* c, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "sfm_warp_pyramid_conv_bwd";
+  WarpPyrArgs A;
+  if (int e = warp_pyr_setup(A, who, d, true, true, c)) return e;
+  if (d->B == 0) return SFM_OK;
+  return warp_pyr_launch_bwd(who, A, d->image_layout == SFM_LAYOUT_HWC, !pose_conv_is_default(A.conv), ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ from ._lib import SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPhotoErro
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
            "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "min_reproj_fwd", "min_reproj_bwd",
-           "disp_smooth_fwd", "disp_smooth_bwd", "warp_full_res_fwd", "warp_full_res_bwd"]
+           "disp_smooth_fwd", "disp_smooth_bwd", "warp_full_res_fwd", "warp_full_res_bwd", "pose_mat_fwd", "pose_mat_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -94,6 +94,69 @@ def pose_proj_bwd(pose6, K, g_proj):
     out = torch.empty((N, 6), dtype=torch.float32, device=pose6.device)
     _launch(pose6.device, lib.sfm_pose_proj_bwd, _p(pose6), _p(K), _p(g_proj), _p(out), N)
     return out
+
+
+def _pose_mat_setting(fmt, invert):
+    fmt = _lib.pose_format_id(fmt)
+    if fmt == _lib.POSE_MATRIX:
+        raise ValueError("pose_format must be 'euler' or 'axis_angle' here: a matrix is what this operator returns")
+    return fmt, int(bool(invert))
+
+
+def pose_mat_fwd(pose6, fmt, invert):
+    """pose6 (N,6) in the convention `fmt` ("euler": the reference's euler2mat / pose_vec2mat; "axis_angle": Monodepth2's
+    rot_from_axisangle and translation) -> T (N,3,4) = [R|t], or [R^T | -R^T t] with `invert` (sfm_pose_mat_fwd)."""
+    fmt, invert = _pose_mat_setting(fmt, invert)
+    pose6 = _dev(pose6, "pose6", 2)
+    N = pose6.shape[0]
+    if pose6.shape[1] != 6:
+        raise TypeError("pose6 must be (N,6)")
+    out = torch.empty((N, 3, 4), dtype=torch.float32, device=pose6.device)
+    _launch(pose6.device, lib.sfm_pose_mat_fwd, _p(pose6), fmt, invert, _p(out), N)
+    return out
+
+
+def pose_mat_bwd(pose6, fmt, invert, g_T):
+    """The backward of `pose_mat_fwd` for g_T (N,3,4) -> d_pose6 (N,6) (sfm_pose_mat_bwd)."""
+    fmt, invert = _pose_mat_setting(fmt, invert)
+    pose6, g_T = _dev(pose6, "pose6", 2), _dev(g_T, "g_T", 3)
+    N = pose6.shape[0]
+    if pose6.shape[1] != 6 or tuple(g_T.shape) != (N, 3, 4) or g_T.device != pose6.device:
+        raise TypeError("pose6 must be (N,6) and g_T (N,3,4) on the same device")
+    out = torch.empty((N, 6), dtype=torch.float32, device=pose6.device)
+    _launch(pose6.device, lib.sfm_pose_mat_bwd, _p(pose6), fmt, invert, _p(g_T), _p(out), N)
+    return out
+
+
+def pose_conv(pose_format="euler", invert=None, depth_affine=None, n_src=None):
+    """The SfmPoseConv of three keyword arguments (include/sfmwarp_pose.h), or None where all three are the defaults -- the caller
+    then uses the existing symbols.  invert: None or one flag per source; depth_affine: None or (disp_scale, disp_shift).  Anything
+    else is a ValueError, raised before a tensor is looked at."""
+    if pose_format == "euler" and invert is None and depth_affine is None:
+        return None
+    fmt = _lib.pose_format_id(pose_format)
+    flags = [] if invert is None else [bool(v) for v in invert]
+    if n_src is not None and invert is not None and len(flags) != n_src:
+        raise ValueError("invert needs one flag per source (%d), got %d" % (n_src, len(flags)))
+    if len(flags) > _lib.SFM_MAX_SRC:
+        raise ValueError("invert: at most %d sources" % _lib.SFM_MAX_SRC)
+    if fmt == _lib.POSE_MATRIX and any(flags):
+        raise ValueError("invert with pose_format='matrix': a general 3x4 has no R^T inverse, invert it before the call")
+    scale, shift = (1.0, 0.0) if depth_affine is None else (float(depth_affine[0]), float(depth_affine[1]))
+    if not (scale - scale == 0.0 and shift - shift == 0.0):
+        raise ValueError("depth_affine must be two finite numbers, got %r" % (depth_affine,))
+    if fmt == _lib.POSE_EULER and not any(flags) and (scale, shift) == (1.0, 0.0):
+        return None
+    c = _lib.SfmPoseConv()
+    c.pose_format, c.disp_scale, c.disp_shift = fmt, scale, shift
+    for i, v in enumerate(flags):
+        c.invert[i] = int(v)
+    return c
+
+
+def _pose_shape(conv):
+    """the shape of one sample's pose under the conventions `conv`"""
+    return (3, 4) if conv is not None and conv.pose_format == _lib.POSE_MATRIX else (6,)
 
 
 def pose_proj_bwd_intrinsics(pose6, K, g_proj):
@@ -451,7 +514,7 @@ def _place_workspace(ws, nbytes, device):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the warp of the whole source pyramid (include/sfmwarp.h)
 # ---------------------------------------------------------------------------------------------------------------------------
-def _warp_pyramid_desc(src_pyr, disps, poses, K, layout):
+def _warp_pyramid_desc(src_pyr, disps, poses, K, layout, pose_shape=(6,)):
     """(descriptor with the inputs bound, the arrays it points at, B, n_src, [(h, w)], device) for warp_pyramid_fwd / _bwd"""
     if layout not in _LAYOUTS:
         raise ValueError("layout must be 'planar' or 'hwc', got %r" % (layout,))
@@ -460,7 +523,7 @@ def _warp_pyramid_desc(src_pyr, disps, poses, K, layout):
     if len(src_pyr) != S or not 1 <= S <= _lib.SFM_MAX_SCALES or not 1 <= n_src <= _lib.SFM_MAX_SRC:
         raise TypeError("src_pyr and disps need one entry per scale (1..%d), poses one per source (1..%d)"
                         % (_lib.SFM_MAX_SCALES, _lib.SFM_MAX_SRC))
-    src_pyr, disps, poses = _devs(src_pyr, "src_pyr", 5 if hwc else 4), _devs(disps, "disps", 4), _devs(poses, "poses", 2)
+    src_pyr, disps, poses = _devs(src_pyr, "src_pyr", 5 if hwc else 4), _devs(disps, "disps", 4), _devs(poses, "poses", 1 + len(pose_shape))
     K = _dev(K, "intrinsics", 4)
     B, dev = disps[0].shape[0], disps[0].device
     if tuple(K.shape) != (B, S, 3, 3):
@@ -472,8 +535,8 @@ def _warp_pyramid_desc(src_pyr, disps, poses, K, layout):
             raise TypeError("scale %d: expected src %s and disp (B,1,h,w), got %s and %s"
                             % (s, want, tuple(src_pyr[s].shape), tuple(disps[s].shape)))
     for i, t in enumerate(poses):
-        if tuple(t.shape) != (B, 6):
-            raise TypeError("poses[%d] must be (B,6)" % i)
+        if tuple(t.shape) != (B,) + pose_shape:
+            raise TypeError("poses[%d] must be %s" % (i, _POSE_SHAPE_NAMES[pose_shape]))
     _one_device(dev, src_pyr + disps + poses + [K])
     d = SfmWarpPyramidDesc()
     d.B, d.n_src, d.image_layout = B, n_src, _LAYOUTS[layout]
@@ -484,24 +547,44 @@ def _warp_pyramid_desc(src_pyr, disps, poses, K, layout):
     return d, (src_pyr, disps, poses, K), B, n_src, hw, dev
 
 
-def warp_pyramid_fwd(src_pyr, disps, poses, K, layout, want_valid=False):
+_POSE_SHAPE_NAMES = {(6,): "(B,6)", (3, 4): "(B,3,4)"}
+
+
+def _warp_pyramid_calls(conv):
+    """(fwd, workspace query, bwd) as callables of the existing signatures: the existing symbols without conventions, those of
+    include/sfmwarp_pose.h with `conv` bound otherwise"""
+    if conv is None:
+        return lib.sfm_warp_pyramid_fwd, lib.sfm_warp_pyramid_bwd_workspace_bytes, lib.sfm_warp_pyramid_bwd
+    c = C.byref(conv)
+    return (lambda d, *rest: lib.sfm_warp_pyramid_conv_fwd(d, c, *rest),
+            lambda d: lib.sfm_warp_pyramid_conv_bwd_workspace_bytes(d, c),
+            lambda d, *rest: lib.sfm_warp_pyramid_conv_bwd(d, c, *rest))
+
+
+def warp_pyramid_fwd(src_pyr, disps, poses, K, layout, want_valid=False, pose_format="euler", invert=None, depth_affine=None):
     """Every scale and source of a step warped in ONE launch (sfm_warp_pyramid_fwd): src_pyr[s] (B,3*n_src,h,w) for layout
     "planar" or (B,n_src,h,w,3) for "hwc" (what `pyramid_hwc` writes), disps[s] (B,1,h,w), poses[i] (B,6), K (B,S,3,3) ->
     [warped_s (B,n_src,3,h,w)], each `warp_fwd` of that (scale, source) with depth 1 / disp bit for bit; with `want_valid` also
-    [valid_s (B,n_src,h,w)]: 1.0 where the sample passes both strict tests of models/transform.py:129, else 0.0."""
-    d, keep, B, n_src, hw, dev = _warp_pyramid_desc(src_pyr, disps, poses, K, layout)
+    [valid_s (B,n_src,h,w)]: 1.0 where the sample passes both strict tests of models/transform.py:129, else 0.0.
+    pose_format, invert, depth_affine: the conventions of include/sfmwarp_pose.h (`pose_conv`); "matrix" takes poses[i] (B,3,4)."""
+    conv = pose_conv(pose_format, invert, depth_affine, len(poses))
+    fwd = _warp_pyramid_calls(conv)[0]
+    d, keep, B, n_src, hw, dev = _warp_pyramid_desc(src_pyr, disps, poses, K, layout, _pose_shape(conv))
     warped = _empty([(B, n_src, 3, h, w) for h, w in hw], dev)
     valid = _empty([(B, n_src, h, w) for h, w in hw], dev) if want_valid else None
     _point(d.warped, warped)
     _point(d.valid, valid or ())
-    _launch(dev, lib.sfm_warp_pyramid_fwd, C.byref(d))
+    _launch(dev, fwd, C.byref(d))
     return (warped, valid) if want_valid else warped
 
 
-def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped):
+def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped, pose_format="euler", invert=None, depth_affine=None):
     """The backward of `warp_pyramid_fwd` for the upstream gradients g_warped[s] (B,n_src,3,h,w): one launch over the pixels and a
-    small fold (sfm_warp_pyramid_bwd) -> ([d_disp_s (B,1,h,w)], [d_pose_i (B,6)]).  No atomics: the same bits on every call."""
-    d, keep, B, n_src, hw, dev = _warp_pyramid_desc(src_pyr, disps, poses, K, layout)
+    small fold (sfm_warp_pyramid_bwd) -> ([d_disp_s (B,1,h,w)], [d_pose_i (B,6)]).  No atomics: the same bits on every call.
+    Under pose_format="matrix" d_pose_i is (B,3,4): the gradient of the matrix itself."""
+    conv = pose_conv(pose_format, invert, depth_affine, len(poses))
+    _, query, bwd = _warp_pyramid_calls(conv)
+    d, keep, B, n_src, hw, dev = _warp_pyramid_desc(src_pyr, disps, poses, K, layout, _pose_shape(conv))
     if len(g_warped) != len(hw):
         raise TypeError("g_warped needs one entry per scale")
     g_warped = _devs(g_warped, "g_warped", 5)
@@ -509,22 +592,22 @@ def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped):
         if tuple(g_warped[s].shape) != (B, n_src, 3, h, w) or g_warped[s].device != dev:
             raise TypeError("g_warped[%d] must be (B,n_src,3,h,w) = %s on %s" % (s, (B, n_src, 3, h, w), dev))
     d_disps = _empty([(B, 1, h, w) for h, w in hw], dev)
-    d_poses = _empty([(B, 6)] * n_src, dev)
+    d_poses = _empty([(B,) + _pose_shape(conv)] * n_src, dev)
     for field, arrays in ((d.g_warped, g_warped), (d.d_disp, d_disps), (d.d_pose, d_poses)):
         _point(field, arrays)
-    nbytes = lib.sfm_warp_pyramid_bwd_workspace_bytes(C.byref(d))
+    nbytes = query(C.byref(d))
     if nbytes == 0:
-        check(lib.sfm_warp_pyramid_bwd(C.byref(d), None, 0, None))   # re-run the validation for its message
+        check(bwd(C.byref(d), None, 0, None))   # re-run the validation for its message
         raise ValueError(_lib.last_error() or "invalid warp pyramid descriptor")
     ws, ptr, have = _place_workspace(None, nbytes, dev)
-    _launch(dev, lib.sfm_warp_pyramid_bwd, C.byref(d), C.c_void_p(ptr), have)
+    _launch(dev, bwd, C.byref(d), C.c_void_p(ptr), have)
     return d_disps, d_poses
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the full-resolution multi-scale warp: every disparity upsampled inside the warp (include/sfmwarp_full_res.h)
 # ---------------------------------------------------------------------------------------------------------------------------
-def _warp_full_res_desc(src, disps, poses, K, layout):
+def _warp_full_res_desc(src, disps, poses, K, layout, pose_shape=(6,)):
     """(descriptor with the inputs bound, the arrays it points at, B, n_src, (H, W), [(h, w)], device) for warp_full_res_fwd / _bwd"""
     if layout not in _LAYOUTS:
         raise ValueError("layout must be 'planar' or 'hwc', got %r" % (layout,))
@@ -532,7 +615,7 @@ def _warp_full_res_desc(src, disps, poses, K, layout):
     S, n_src = len(disps), len(poses)
     if not 1 <= S <= _lib.SFM_MAX_SCALES or not 1 <= n_src <= _lib.SFM_MAX_SRC:
         raise TypeError("disps needs one entry per scale (1..%d), poses one per source (1..%d)" % (_lib.SFM_MAX_SCALES, _lib.SFM_MAX_SRC))
-    src, disps, poses = _dev(src, "src", 5 if hwc else 4), _devs(disps, "disps", 4), _devs(poses, "poses", 2)
+    src, disps, poses = _dev(src, "src", 5 if hwc else 4), _devs(disps, "disps", 4), _devs(poses, "poses", 1 + len(pose_shape))
     K = _dev(K, "intrinsics", 3)
     B, dev = src.shape[0], src.device
     H, W = (src.shape[2:4] if hwc else src.shape[2:])
@@ -544,8 +627,8 @@ def _warp_full_res_desc(src, disps, poses, K, layout):
         if tuple(t.shape[:2]) != (B, 1):
             raise TypeError("disps[%d] must be (B,1,h,w) = (%d,1,h,w), got %s" % (s, B, tuple(t.shape)))
     for i, t in enumerate(poses):
-        if tuple(t.shape) != (B, 6):
-            raise TypeError("poses[%d] must be (B,6)" % i)
+        if tuple(t.shape) != (B,) + pose_shape:
+            raise TypeError("poses[%d] must be %s" % (i, _POSE_SHAPE_NAMES[pose_shape]))
     _one_device(dev, disps + poses + [K])
     hw = [tuple(t.shape[2:]) for t in disps]
     d = SfmWarpFullResDesc()
@@ -556,6 +639,17 @@ def _warp_full_res_desc(src, disps, poses, K, layout):
     for field, arrays in ((d.disp, disps), (d.pose, poses)):
         _point(field, arrays)
     return d, (src, disps, poses, K), B, n_src, (H, W), hw, dev
+
+
+def _warp_full_res_conv_calls(upsample, conv):
+    """`_warp_full_res_calls` under the conventions `conv` (`pose_conv`): without any (None) exactly that; otherwise the entry points
+    of include/sfmwarp_pose.h with the upsampling and the conventions bound"""
+    if conv is None:
+        return _warp_full_res_calls(upsample)
+    up, c = _lib.upsample_id(upsample), C.byref(conv)
+    return (lambda d, *rest: lib.sfm_warp_full_res_conv_fwd(d, up, c, *rest),
+            lambda d: lib.sfm_warp_full_res_conv_bwd_workspace_bytes(d, up, c),
+            lambda d, *rest: lib.sfm_warp_full_res_conv_bwd(d, up, c, *rest))
 
 
 def _warp_full_res_calls(upsample):
@@ -569,14 +663,18 @@ def _warp_full_res_calls(upsample):
             lambda d, *rest: lib.sfm_warp_full_res_up_bwd(d, up, *rest))
 
 
-def warp_full_res_fwd(src, disps, poses, K, layout, want_valid=False, upsample="align_corners"):
+def warp_full_res_fwd(src, disps, poses, K, layout, want_valid=False, upsample="align_corners", pose_format="euler", invert=None,
+                      depth_affine=None):
     """ONE full-resolution source set warped with the disparity of every scale, each upsampled to (H, W) inside the kernel, in ONE
     launch (sfm_warp_full_res_fwd): src (B,3*n_src,H,W) for layout "planar" or (B,n_src,H,W,3) for "hwc", disps[s] (B,1,h_s,w_s) of any
     sizes, poses[i] (B,6), K (B,3,3) -> [warped_s (B,n_src,3,H,W)]: `warp_pyramid_fwd` at equal sizes on `resize` of each disparity
     (itself where it has the full size), bit for bit; with `want_valid` also [valid_s (B,n_src,H,W)].  upsample="half_pixel": each
-    disparity upsampled as F.interpolate(mode="bilinear", align_corners=False) does instead (sfm_warp_full_res_up_fwd)."""
-    fwd = _warp_full_res_calls(upsample)[0]
-    d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout)
+    disparity upsampled as F.interpolate(mode="bilinear", align_corners=False) does instead (sfm_warp_full_res_up_fwd).
+    pose_format, invert, depth_affine: the conventions of include/sfmwarp_pose.h (`pose_conv`); the affine map acts on the
+    upsampled disparity; "matrix" takes poses[i] (B,3,4)."""
+    conv = pose_conv(pose_format, invert, depth_affine, len(poses))
+    fwd = _warp_full_res_conv_calls(upsample, conv)[0]
+    d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout, _pose_shape(conv))
     warped = _empty([(B, n_src, 3, H, W)] * len(hw), dev)
     valid = _empty([(B, n_src, H, W)] * len(hw), dev) if want_valid else None
     _point(d.warped, warped)
@@ -585,14 +683,17 @@ def warp_full_res_fwd(src, disps, poses, K, layout, want_valid=False, upsample="
     return (warped, valid) if want_valid else warped
 
 
-def warp_full_res_bwd(src, disps, poses, K, layout, g_warped, ws=None, upsample="align_corners"):
+def warp_full_res_bwd(src, disps, poses, K, layout, g_warped, ws=None, upsample="align_corners", pose_format="euler", invert=None,
+                      depth_affine=None):
     """The backward of `warp_full_res_fwd` for the upstream gradients g_warped[s] (B,n_src,3,H,W): one launch over the pixels, one
     that gathers every low-resolution gradient and a small fold (sfm_warp_full_res_bwd) -> ([d_disp_s (B,1,h_s,w_s)], [d_pose_i
     (B,6)]): `warp_pyramid_bwd` at equal sizes followed by `resize_bwd` of each d_disp, bit for bit.  No atomics: the same bits on
     every call, whatever `ws` (the caller's workspace, or None for a fresh one) held.  upsample="half_pixel": the backward of that
-    forward (sfm_warp_full_res_up_bwd), each d_disp the adjoint of the half-pixel upsampling; the workspace is the same."""
-    _, query, bwd = _warp_full_res_calls(upsample)
-    d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout)
+    forward (sfm_warp_full_res_up_bwd), each d_disp the adjoint of the half-pixel upsampling; the workspace is the same.
+    Under pose_format="matrix" d_pose_i is (B,3,4): the gradient of the matrix itself."""
+    conv = pose_conv(pose_format, invert, depth_affine, len(poses))
+    _, query, bwd = _warp_full_res_conv_calls(upsample, conv)
+    d, keep, B, n_src, (H, W), hw, dev = _warp_full_res_desc(src, disps, poses, K, layout, _pose_shape(conv))
     if len(g_warped) != len(hw):
         raise TypeError("g_warped needs one entry per scale")
     g_warped = _devs(g_warped, "g_warped", 5)
@@ -600,7 +701,7 @@ def warp_full_res_bwd(src, disps, poses, K, layout, g_warped, ws=None, upsample=
         if tuple(g.shape) != (B, n_src, 3, H, W) or g.device != dev:
             raise TypeError("g_warped[%d] must be (B,n_src,3,H,W) = %s on %s" % (s, (B, n_src, 3, H, W), dev))
     d_disps = _empty([(B, 1, h, w) for h, w in hw], dev)
-    d_poses = _empty([(B, 6)] * n_src, dev)
+    d_poses = _empty([(B,) + _pose_shape(conv)] * n_src, dev)
     for field, arrays in ((d.g_warped, g_warped), (d.d_disp, d_disps), (d.d_pose, d_poses)):
         _point(field, arrays)
     nbytes = query(C.byref(d))

@@ -9,6 +9,8 @@ grad_fn.  This module hands those outputs to libsfmwarp and the gradients it com
                                       loss of the caller's own (ops.pyramid_hwc, ops.warp_pyramid_fwd / ops.warp_pyramid_bwd)
   warp_full_res                       the full-resolution sources warped with the disparity of EVERY scale, each upsampled inside the
                                       warp: Monodepth2's full-resolution multi-scale (ops.warp_full_res_fwd / ops.warp_full_res_bwd)
+  pose_matrix                         a 6-vector (axis-angle or Euler, optionally inverted) -> the rigid 3x4 the warps take with
+                                      pose_format="matrix": Monodepth2's transformation_from_parameters (ops.pose_mat_fwd / ops.pose_mat_bwd)
   photometric_error                   alpha * SSIM + (1 - alpha) * L1 per pixel (models/base_model.py:96,126-142) of every (scale, image) of
                                       a step, differentiable w.r.t. the images (ops.photo_error_fwd / ops.photo_error_bwd)
   min_reprojection                    the stage behind it: per pixel the minimum over the sources, the auto-mask against the unwarped
@@ -45,7 +47,7 @@ from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
            "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error",
-           "min_reprojection", "min_reprojection_loss", "disparity_smoothness", "warp_full_res"]
+           "min_reprojection", "min_reprojection_loss", "disparity_smoothness", "warp_full_res", "pose_matrix"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -347,9 +349,68 @@ def _dev_float(t, name, ndim=None):
     return t if t.dtype == torch.float32 else t.to(torch.float32)
 
 
-def _poses(pred_poses, B, n_src):
+_EULER = ("euler", None, None)
+
+
+def _pose_conv_args(src_imgs, pose_format, invert, depth_range):
+    """The three convention arguments of the warps, checked before any array is: -> (pose_format, invert as a tuple of bools or None,
+    (disp_scale, disp_shift) or None), what ops.warp_*'s keyword arguments of the same meaning take.  depth_range = (min_depth,
+    max_depth) is Monodepth2's disp_to_depth: depth = 1 / (1/max_depth + (1/min_depth - 1/max_depth) * disp)."""
+    if pose_format == "euler" and invert is None and depth_range is None:      # the existing call: nothing to look at
+        return _EULER
+    fmt = _lib.pose_format_id(pose_format)
+    if invert is not None:
+        if isinstance(invert, (bool, int, float, torch.Tensor)) or not all(isinstance(v, (bool, int)) and v in (0, 1) for v in invert):
+            raise ValueError("invert must be None or a sequence of one boolean per source, got %r" % (invert,))
+        invert = tuple(bool(v) for v in invert)
+        n_src = src_imgs.shape[1] if isinstance(src_imgs, torch.Tensor) and src_imgs.dim() == 5 else None
+        if n_src is not None and len(invert) != n_src:
+            raise ValueError("invert needs one boolean per source (%d), got %d" % (n_src, len(invert)))
+        if fmt == _lib.POSE_MATRIX and any(invert):
+            raise ValueError("invert with pose_format='matrix': a general 3x4 has no R^T inverse -- invert the matrices before the call "
+                             "(pose_matrix(..., invert=True) does it for a rigid one)")
+    affine = None
+    if depth_range is not None:
+        try:
+            lo, hi = (float(v) for v in depth_range)
+        except (TypeError, ValueError):
+            raise ValueError("depth_range must be None or (min_depth, max_depth), got %r" % (depth_range,)) from None
+        if not (0.0 < lo < hi < float("inf")):
+            raise ValueError("depth_range needs 0 < min_depth < max_depth, both finite, got %r" % (depth_range,))
+        affine = (1.0 / lo - 1.0 / hi, 1.0 / hi)
+    return pose_format, invert, affine
+
+
+def _pose_kw(pc):
+    return dict(pose_format=pc[0], invert=pc[1], depth_affine=pc[2])
+
+
+def _pose_matrices(pred_poses, B, n_src):
+    """pose_format="matrix": a list of n_src (B,3,4) or (B,4,4) tensors, or one (B,n_src,3,4) / (B,n_src,4,4) tensor -> n_src contiguous
+    float32 (B,3,4) arrays, rows 0..2 of each (the slice and the cast are recorded by autograd: the gradient returns in the input's
+    shape and dtype, a fourth row's is 0)."""
+    if isinstance(pred_poses, torch.Tensor):
+        t = _dev_float(pred_poses, "pred_poses", 4)
+        if tuple(t.shape) not in ((B, n_src, 3, 4), (B, n_src, 4, 4)):
+            raise TypeError("pred_poses: expected (B,n_src,3,4) or (B,n_src,4,4) with B, n_src = %d, %d, got %s" % (B, n_src, tuple(t.shape)))
+        return [t[:, i, :3].contiguous() for i in range(n_src)]
+    poses = list(pred_poses)
+    if len(poses) != n_src:
+        raise TypeError("src_imgs has %d sources but %d poses were given" % (n_src, len(poses)))
+    out = []
+    for i, t in enumerate(poses):
+        t = _dev_float(t, "pred_poses[%d]" % i, 3)
+        if tuple(t.shape) not in ((B, 3, 4), (B, 4, 4)):
+            raise TypeError("pred_poses[%d] must be (B,3,4) or (B,4,4) with B = %d, got %s" % (i, B, tuple(t.shape)))
+        out.append(t[:, :3].contiguous())
+    return out
+
+
+def _poses(pred_poses, B, n_src, pose_format="euler"):
     """A list of n_src (B,6) tensors (contiguous or not, e.g. h.split(6, 1)) or PoseNet's packed (B,6*n_src) output ->
-    n_src contiguous float32 (B,6) arrays."""
+    n_src contiguous float32 (B,6) arrays.  pose_format="matrix": `_pose_matrices`."""
+    if pose_format == "matrix":
+        return _pose_matrices(pred_poses, B, n_src)
     if isinstance(pred_poses, torch.Tensor):
         packed = _dev_float(pred_poses, "pred_poses", 2)
         if tuple(packed.shape) != (B, 6 * n_src):
@@ -380,7 +441,7 @@ def _masks(pred_maskes, B, n_src, H, W, S):
     return masks
 
 
-def _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt=None, exp_reg=0.0, pred_maskes=None):
+def _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt=None, exp_reg=0.0, pred_maskes=None, pose_format="euler"):
     """The inputs of `sfm_learner_loss` (which passes `tgt`, its checked target frames) and of `warp_pyramid` (which does not, and
     takes the intrinsics as constants), checked in the one order both have: src_imgs (B,n_src,3,H,W) -- with `tgt`, that it is
     (B,3,H,W) too --, 1..8 sources, 1..8 scales, intrinsics (B,S,3,3), pred_disps[s] (B,1,H>>s,W>>s), the poses, with exp_reg > 0
@@ -409,7 +470,7 @@ def _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt=None, exp_reg
         if tuple(t.shape) != (B, 1, H >> s, W >> s):
             raise TypeError("pred_disps[%d] must be (B,1,H>>%d,W>>%d) = %s, got %s" % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
         disps.append(t)
-    poses = _poses(pred_poses, B, n_src)
+    poses = _poses(pred_poses, B, n_src, pose_format)
     masks = _masks(pred_maskes, B, n_src, H, W, S) if exp_reg > 0 else []
     dev = src.device if tgt is None else tgt.device
     for t in [K] + disps + poses + masks:
@@ -519,15 +580,47 @@ def projective_inverse_warp(imgs, depthes, poses, K):
     return _Warp.apply(imgs, depthes, poses, K)
 
 
+class _PoseMatrix(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pose, fmt, invert):
+        ctx.save_for_backward(pose)
+        ctx.conv = (fmt, invert)
+        return ops.pose_mat_fwd(pose, fmt, invert)
+
+    @staticmethod
+    def backward(ctx, g):
+        pose, = ctx.saved_tensors
+        return ops.pose_mat_bwd(pose, *ctx.conv, g.to(torch.float32).contiguous()), None, None
+
+
+def pose_matrix(pose, *, pose_format="axis_angle", invert=False):
+    """pose (B,6) -> the rigid transform T (B,3,4) = [R|t] as ONE differentiable node (ops.pose_mat_fwd / ops.pose_mat_bwd):
+    pose_format="axis_angle": (ax, ay, az, tx, ty, tz), R Monodepth2's rot_from_axisangle (any finite angle); "euler": the reference's
+    euler2mat / pose_vec2mat.  invert=True returns [R^T | -R^T t], Monodepth2's transformation_from_parameters(..., invert=True).
+    float32, bfloat16 or float16 on a ROCm device, computed in float32, the gradient returned in the input's dtype.
+
+    What it is for: build every source's matrix your own way -- a pose head per source, a fixed stereo baseline, the product of two
+    poses (append the row (0,0,0,1) and matmul) -- and hand the result to `warp_pyramid`, `warp_full_res` or
+    `min_reprojection_loss` with pose_format="matrix"."""
+    if _lib.pose_format_id(pose_format) == _lib.POSE_MATRIX:
+        raise ValueError("pose_format must be 'euler' or 'axis_angle': a matrix is what pose_matrix returns")
+    if not isinstance(invert, (bool, int)) or invert not in (0, 1):
+        raise ValueError("invert must be a boolean, got %r" % (invert,))
+    pose = _dev_float(pose, "pose", 2)
+    if pose.shape[1] != 6:
+        raise TypeError("pose must be (B,6), got %s" % (tuple(pose.shape),))
+    return _PoseMatrix.apply(pose, pose_format, bool(invert))
+
+
 class _WarpPyramid(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, src, K, S, want_valid, *arrays):
+    def forward(ctx, src, K, S, want_valid, pc, *arrays):
         disps, poses = list(arrays[:S]), list(arrays[S:])
         pyr = ops.pyramid_hwc(src, S)
-        out = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", want_valid)
+        out = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", want_valid, **_pose_kw(pc))
         warped, valid = out if want_valid else (out, [])
         ctx.save_for_backward(K, *pyr, *disps, *poses)
-        ctx.S = S
+        ctx.S, ctx.pc = S, pc
         ctx.mark_non_differentiable(*valid)
         ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
         return tuple(warped) + tuple(valid)
@@ -540,11 +633,11 @@ class _WarpPyramid(torch.autograd.Function):
         B, n_src = pyr[0].shape[:2]
         g = [torch.zeros((B, n_src, 3) + tuple(d.shape[2:]), dtype=torch.float32, device=d.device) if gr is None
              else gr.to(torch.float32).contiguous() for gr, d in zip(grads[:S], disps)]
-        d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", g)
-        return (None, None, None, None) + tuple(d_disps) + tuple(d_poses)
+        d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", g, **_pose_kw(ctx.pc))
+        return (None, None, None, None, None) + tuple(d_disps) + tuple(d_poses)
 
 
-def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False):
+def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False, pose_format="euler", invert=None, depth_range=None):
     """The warped source images of every scale and every source of a step -- curr_proj_img of models/base_model.py:90-94 for all s
     and i -- as differentiable tensors, for a loss of your own on them (a per-pixel minimum over the sources, auto-masking, a
     robust penalty, a feature loss).  The inputs are those of `sfm_learner_loss`:
@@ -560,23 +653,33 @@ def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=F
     1.0 where the sample passes both strict tests of models/transform.py:129, else 0.0 (not differentiable).
 
     Two launches forward (the source pyramid, the warp of all scales and sources); backward one launch over the pixels plus a small
-    fold, whatever S and n_src are.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture."""
-    src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses)
+    fold, whatever S and n_src are.  Nothing reads a device value on the host: it runs under torch.cuda.graph capture.
+
+    pose_format, invert and depth_range select the pose and depth conventions inside the same launches (include/sfmwarp_pose.h):
+    pose_format="axis_angle": pred_poses[i] = (ax, ay, az, tx, ty, tz), R Monodepth2's rot_from_axisangle; "matrix": pred_poses is a
+      list of n_src (B,3,4) or (B,4,4) tensors (rows 0..2 are used) or one (B,n_src,3,4) / (B,n_src,4,4) tensor, any 3x4, and the
+      gradient is that of the matrix, in the input's shape (`pose_matrix` builds one from a 6-vector, differentiably);
+    invert: None or n_src booleans -- source i is warped through [R^T | -R^T t], Monodepth2's invert=True (a ValueError with "matrix");
+    depth_range=(min_depth, max_depth): depth = 1 / (1/max_depth + (1/min_depth - 1/max_depth) * disp), Monodepth2's disp_to_depth,
+      instead of 1 / disp.
+    With the three at their defaults the call is what it was, bit for bit."""
+    pc = _pose_conv_args(src_imgs, pose_format, invert, depth_range)
+    src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, pose_format=pose_format)
     B, n_src, _, H, W = src.shape
     S = len(disps)
-    out = _WarpPyramid.apply(src.view(B, 3 * n_src, H, W), K, S, bool(return_valid), *disps, *poses)
+    out = _WarpPyramid.apply(src.view(B, 3 * n_src, H, W), K, S, bool(return_valid), pc, *disps, *poses)
     return (list(out[:S]), list(out[S:])) if return_valid else list(out)
 
 
 class _WarpFullRes(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, src, K, S, want_valid, upsample, *arrays):
+    def forward(ctx, src, K, S, want_valid, upsample, pc, *arrays):
         disps, poses = list(arrays[:S]), list(arrays[S:])
         hwc = ops.pyramid_hwc(src, 1)[0]
-        out = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", want_valid, upsample=upsample)
+        out = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", want_valid, upsample=upsample, **_pose_kw(pc))
         warped, valid = out if want_valid else (out, [])
         ctx.save_for_backward(K, hwc, *disps, *poses)
-        ctx.S, ctx.upsample = S, upsample
+        ctx.S, ctx.upsample, ctx.pc = S, upsample, pc
         ctx.mark_non_differentiable(*valid)
         ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
         return tuple(warped) + tuple(valid)
@@ -589,11 +692,11 @@ class _WarpFullRes(torch.autograd.Function):
         B, n_src, H, W = hwc.shape[:4]
         g = [torch.zeros((B, n_src, 3, H, W), dtype=torch.float32, device=hwc.device) if gr is None
              else gr.to(torch.float32).contiguous() for gr in grads[:S]]
-        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", g, upsample=ctx.upsample)
-        return (None, None, None, None, None) + tuple(d_disps) + tuple(d_poses)
+        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", g, upsample=ctx.upsample, **_pose_kw(ctx.pc))
+        return (None, None, None, None, None, None) + tuple(d_disps) + tuple(d_poses)
 
 
-def _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, who):
+def _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, who, pose_format="euler"):
     """The inputs of `warp_full_res`, checked: src_imgs (B,n_src,3,H,W), 1..8 sources, 1..8 scales, intrinsics (B,3,3) or (B,S,3,3)
     -- of which [:, 0], the full-resolution camera, is used --, a constant, pred_disps[s] (B,1,h_s,w_s) of any size, the poses, and
     last that every array lives on the frames' device.  -> (src, K (B,3,3), disps, poses)"""
@@ -620,14 +723,15 @@ def _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, who):
         if tuple(t.shape[:2]) != (B, 1):
             raise TypeError("pred_disps[%d] must be (B,1,h,w) = (%d,1,h,w), got %s" % (s, B, tuple(t.shape)))
         disps.append(t)
-    poses = _poses(pred_poses, B, n_src)
+    poses = _poses(pred_poses, B, n_src, pose_format)
     for t in [K] + disps + poses:
         if t.device != src.device:
             raise TypeError("every array must live on %s, one is on %s" % (src.device, t.device))
     return src, K, disps, poses
 
 
-def warp_full_res(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False, upsample="align_corners"):
+def warp_full_res(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=False, upsample="align_corners", pose_format="euler",
+                  invert=None, depth_range=None):
     """Monodepth2's "full-resolution multi-scale" warp: the disparity of every scale upsampled to the input resolution and the
     FULL-RESOLUTION sources warped with it through the full-resolution camera -- what `resize_images` per scale followed by
     `projective_inverse_warp` per (scale, source) computes, in one launch and without a full-resolution copy of any disparity.
@@ -648,12 +752,16 @@ def warp_full_res(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=
 
     upsample="half_pixel" is Monodepth2's own upsampling instead: every resampled disparity is F.interpolate(pred_disps[s], (H, W),
     mode="bilinear", align_corners=False) -- half-pixel centres -- formed inside the same launch, its gradient the adjoint of that map
-    in the same gather launch.  The launches, the workspace and the determinism are those of the default; any other name is a ValueError."""
+    in the same gather launch.  The launches, the workspace and the determinism are those of the default; any other name is a ValueError.
+
+    pose_format, invert, depth_range: as in `warp_pyramid`; the depth map acts on the UPSAMPLED disparity, as Monodepth2's
+    disp_to_depth(F.interpolate(disp, ...)) does."""
     _lib.upsample_id(upsample)
-    src, K, disps, poses = _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, "warp_full_res")
+    pc = _pose_conv_args(src_imgs, pose_format, invert, depth_range)
+    src, K, disps, poses = _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, "warp_full_res", pose_format)
     B, n_src, _, H, W = src.shape
     S = len(disps)
-    out = _WarpFullRes.apply(src.detach().view(B, 3 * n_src, H, W), K, S, bool(return_valid), upsample, *disps, *poses)
+    out = _WarpFullRes.apply(src.detach().view(B, 3 * n_src, H, W), K, S, bool(return_valid), upsample, pc, *disps, *poses)
     return (list(out[:S]), list(out[S:])) if return_valid else list(out)
 
 
@@ -891,11 +999,11 @@ class _MinReprojLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tgt, src, K, cfg, S, *arrays):
-        ssim_rate, auto_mask, weights, norm, smooth, pad, _ = cfg
+        ssim_rate, auto_mask, weights, norm, smooth, pad, _, pc = cfg
         disps, poses = list(arrays[:S]), list(arrays[S:])
         B, n_src = src.shape[0], len(poses)
         pyr = ops.pyramid_hwc(src, S)
-        warped, valid = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", True)
+        warped, valid = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", True, **_pose_kw(pc))
         tgts = ops.pyramid(tgt, S)
         errs = ops.photo_error_fwd(warped, tgts, ssim_rate, pad)
         idents = None
@@ -904,11 +1012,11 @@ class _MinReprojLoss(torch.autograd.Function):
         loss, count, winners = ops.min_reproj_fwd(errs, valid, idents, weights, norm)
         if smooth is None:
             ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners)
-            ctx.cfg, ctx.pad = (S, n_src, ssim_rate, weights, norm, None), pad
+            ctx.cfg, ctx.pad, ctx.pc = (S, n_src, ssim_rate, weights, norm, None), pad, pc
             return loss[S]
-        sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)      # on the target pyramid this node holds anyway
+        sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)      # on the target pyramid this node holds anyway: the RAW disparities
         ctx.save_for_backward(K, count, *pyr, *disps, *poses, *warped, *tgts, *winners, stats)
-        ctx.cfg, ctx.pad = (S, n_src, ssim_rate, weights, norm, smooth), pad
+        ctx.cfg, ctx.pad, ctx.pc = (S, n_src, ssim_rate, weights, norm, smooth), pad, pc
         return loss[S] + sm_loss[S]
 
     @staticmethod
@@ -923,7 +1031,7 @@ class _MinReprojLoss(torch.autograd.Function):
         g_loss = _g_loss(S, g_total, None, count.device)
         g_errs = ops.min_reproj_bwd(winners, count, g_loss, n_src, weights, norm, [tuple(t.shape[2:]) for t in disps])
         d_warped = ops.photo_error_bwd(warped, tgts, ssim_rate, g_errs, ctx.pad)
-        d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", d_warped)
+        d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", d_warped, **_pose_kw(ctx.pc))
         if smooth is not None:      # the smoothness gradient is added in place by its kernel: no aten call
             ops.disp_smooth_bwd(disps, tgts, rest[3 * S], g_loss, *smooth, out=d_disps)
         return (None,) * 5 + tuple(d_disps) + tuple(d_poses)
@@ -935,12 +1043,12 @@ class _MinReprojLossFullRes(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tgt, src, K, cfg, S, *arrays):
-        ssim_rate, auto_mask, weights, norm, smooth, pad, up = cfg
+        ssim_rate, auto_mask, weights, norm, smooth, pad, up, pc = cfg
         disps, poses = list(arrays[:S]), list(arrays[S:])
         B, n_src = src.shape[0], len(poses)
         H, W = tgt.shape[2:]
         hwc = ops.pyramid_hwc(src, 1)[0]
-        warped, valid = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", True, upsample=up)
+        warped, valid = ops.warp_full_res_fwd(hwc, disps, poses, K, "hwc", True, upsample=up, **_pose_kw(pc))
         errs = ops.photo_error_fwd(warped, [tgt] * S, ssim_rate, pad)
         idents = None
         if auto_mask:     # the identity reprojection, ONCE: the target and the unwarped sources are the same at every scale
@@ -948,12 +1056,12 @@ class _MinReprojLossFullRes(torch.autograd.Function):
         loss, count, winners = ops.min_reproj_fwd(errs, valid, idents, weights, norm)
         if smooth is None:
             ctx.save_for_backward(K, count, hwc, tgt, *disps, *poses, *warped, *winners)
-            ctx.cfg, ctx.conv = (S, n_src, ssim_rate, weights, norm, None), (pad, up)
+            ctx.cfg, ctx.conv, ctx.pc = (S, n_src, ssim_rate, weights, norm, None), (pad, up), pc
             return loss[S]
         tgts = ops.pyramid(tgt, S)
         sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)
         ctx.save_for_backward(K, count, hwc, tgt, *disps, *poses, *warped, *winners, stats, *tgts[1:])
-        ctx.cfg, ctx.conv = (S, n_src, ssim_rate, weights, norm, smooth), (pad, up)
+        ctx.cfg, ctx.conv, ctx.pc = (S, n_src, ssim_rate, weights, norm, smooth), (pad, up), pc
         return loss[S] + sm_loss[S]
 
     @staticmethod
@@ -970,7 +1078,7 @@ class _MinReprojLossFullRes(torch.autograd.Function):
         g_errs = ops.min_reproj_bwd(winners, count, g_loss, n_src, weights, norm, [tuple(tgt.shape[2:])] * S)
         pad, up = ctx.conv
         d_warped = ops.photo_error_bwd(warped, [tgt] * S, ssim_rate, g_errs, pad)
-        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", d_warped, upsample=up)
+        d_disps, d_poses = ops.warp_full_res_bwd(hwc, disps, poses, K, "hwc", d_warped, upsample=up, **_pose_kw(ctx.pc))
         if smooth is not None:      # the smoothness gradient is added in place by its kernel: no aten call
             ops.disp_smooth_bwd(disps, [tgt] + rest[2 * S + 1:], rest[2 * S], g_loss, *smooth, out=d_disps)
         return (None,) * 5 + tuple(d_disps) + tuple(d_poses)
@@ -978,7 +1086,7 @@ class _MinReprojLossFullRes(torch.autograd.Function):
 
 def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses, *, ssim_rate, auto_mask=True, weights=None, norm="kept",
                           smooth_weight=0.0, smooth_normalize=True, smooth_edge="mean_abs", full_res=False, ssim_padding="zero",
-                          upsample="align_corners"):
+                          upsample="align_corners", pose_format="euler", invert=None, depth_range=None):
     """The Monodepth2-style loss of INTEGRATION.md ("Your own loss on the library's warp") in one call and ONE autograd node: per
     pixel the smallest ssim_rate * SSIM + (1 - ssim_rate) * L1 error over the warped sources that are in view, averaged per scale
     over the pixels where it is strictly below the error of every UNWARPED source (`auto_mask`; off: over the pixels some source
@@ -1010,8 +1118,14 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
     ssim_padding="reflect" and upsample="half_pixel" are Monodepth2's own conventions, the `padding` of `photometric_error` -- applied
     to the warped error and to the identity error alike -- and the `upsample` of `warp_full_res`; the smoothness term looks at neither.
     Still one node with the same launches, and still the stages called one after the other with these arguments, bit for bit.
-    upsample="half_pixel" without full_res=True raises ValueError (the pyramid form upsamples nothing), as does any unknown name."""
+    upsample="half_pixel" without full_res=True raises ValueError (the pyramid form upsamples nothing), as does any unknown name.
+
+    pose_format, invert and depth_range are those of `warp_pyramid` / `warp_full_res` and reach the WARP only: the smoothness term
+    keeps reading the raw pred_disps, which is Monodepth2's own split (disp_to_depth in front of the warp, the sigmoid output in the
+    smoothness term).  pose_format="axis_angle", invert=[True, False] and depth_range=(0.1, 100.0) are that code's
+    transformation_from_parameters and disp_to_depth.  Still one node with the same launches; at their defaults the call is what it was."""
     _lib.ssim_padding_id(ssim_padding, "ssim_padding")
+    pc = _pose_conv_args(src_imgs, pose_format, invert, depth_range)
     if _lib.upsample_id(upsample) != _lib.UPSAMPLE_ALIGN_CORNERS and not full_res:
         raise ValueError("upsample=%r needs full_res=True: the pyramid form compares every disparity at its own size" % (upsample,))
     if smooth_weight:       # (0, the default: nothing below is looked at, the call costs what it cost before the term existed)
@@ -1021,7 +1135,7 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
         _lib.disp_smooth_edge_id(smooth_edge)
     tgt = ops._dev(tgt_img, "tgt_img", 4)
     if full_res:
-        src, K, disps, poses = _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, "min_reprojection_loss")
+        src, K, disps, poses = _full_res_inputs(src_imgs, intrinsics, pred_disps, pred_poses, "min_reprojection_loss", pose_format)
         B, n_src, _, H, W = src.shape
         if tuple(tgt.shape) != (B, 3, H, W) or tgt.device != src.device:
             raise TypeError("tgt_img must be (B,3,H,W) = %s on %s, got %s on %s" % ((B, 3, H, W), src.device, tuple(tgt.shape), tgt.device))
@@ -1031,7 +1145,7 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
                                 % (s, s, s, (B, 1, H >> s, W >> s), tuple(t.shape)))
         node = _MinReprojLossFullRes
     else:
-        src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt)
+        src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, pred_disps, pred_poses, tgt, pose_format=pose_format)
         if K.requires_grad:
             raise TypeError("min_reprojection_loss does not differentiate the intrinsics: detach them")
         B, n_src, _, H, W = src.shape
@@ -1039,7 +1153,7 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
     S = len(disps)
     weights = _scale_weights(weights, S)
     smooth = (tuple(smooth_weight * w for w in weights), bool(smooth_normalize), smooth_edge) if smooth_weight else None
-    cfg = (float(ssim_rate), bool(auto_mask), weights, norm, smooth, ssim_padding, upsample)
+    cfg = (float(ssim_rate), bool(auto_mask), weights, norm, smooth, ssim_padding, upsample, pc)
     _lib.min_reproj_norm_id(norm)
     return node.apply(tgt.detach(), src.detach().view(B, 3 * n_src, H, W), K, cfg, S, *disps, *poses)
 
