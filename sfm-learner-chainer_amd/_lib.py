@@ -170,6 +170,19 @@ class SfmPoseConv(C.Structure):
     _fields_ = [("pose_format", C.c_int32), ("invert", C.c_int32 * SFM_MAX_SRC), ("disp_scale", C.c_float), ("disp_shift", C.c_float)]
 
 
+# include/sfmwarp_depth_consistency.h: the geometry-consistency term of SC-SfMLearner
+class SfmDepthConsDesc(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32), ("n_src", C.c_int32), ("n_scales", C.c_int32),
+        ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
+        ("disp", _FP * SFM_MAX_SCALES), ("src_disp", _FP * SFM_MAX_SCALES), ("intrinsics", _FP), ("pose", _FP * SFM_MAX_SRC),
+        ("diff", _FP * SFM_MAX_SCALES), ("valid", _FP * SFM_MAX_SCALES),
+        ("computed", _FP * SFM_MAX_SCALES), ("projected", _FP * SFM_MAX_SCALES),
+        ("g_diff", _FP * SFM_MAX_SCALES), ("d_disp", _FP * SFM_MAX_SCALES), ("d_src_disp", _FP * SFM_MAX_SCALES),
+        ("d_pose", _FP * SFM_MAX_SRC),
+    ]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -269,6 +282,14 @@ POSE_SYMBOLS = {
 }
 
 
+# every symbol declared in the side header include/sfmwarp_depth_consistency.h (to be folded into SYMBOLS together with that header)
+DEPTH_CONS_SYMBOLS = {
+    "sfm_depth_consistency_fwd": (_I, [C.POINTER(SfmDepthConsDesc), C.POINTER(SfmPoseConv), _V]),
+    "sfm_depth_consistency_bwd_workspace_bytes": (_Z, [C.POINTER(SfmDepthConsDesc), C.POINTER(SfmPoseConv)]),
+    "sfm_depth_consistency_bwd": (_I, [C.POINTER(SfmDepthConsDesc), C.POINTER(SfmPoseConv), _V, _Z, _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -280,7 +301,7 @@ def _load():
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SMOOTH_SYMBOLS.items()) \
-            + list(FULL_RES_SYMBOLS.items()) + list(CONV_SYMBOLS.items()) + list(POSE_SYMBOLS.items()):
+            + list(FULL_RES_SYMBOLS.items()) + list(CONV_SYMBOLS.items()) + list(POSE_SYMBOLS.items()) + list(DEPTH_CONS_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -9,12 +9,13 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpFullResDesc, SfmWarpPyramidDesc, check, lib
+from ._lib import SfmDepthConsDesc, SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpFullResDesc, SfmWarpPyramidDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
            "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "min_reproj_fwd", "min_reproj_bwd",
-           "disp_smooth_fwd", "disp_smooth_bwd", "warp_full_res_fwd", "warp_full_res_bwd", "pose_mat_fwd", "pose_mat_bwd"]
+           "disp_smooth_fwd", "disp_smooth_bwd", "warp_full_res_fwd", "warp_full_res_bwd", "pose_mat_fwd", "pose_mat_bwd",
+           "depth_consistency_fwd", "depth_consistency_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -602,6 +603,94 @@ def warp_pyramid_bwd(src_pyr, disps, poses, K, layout, g_warped, pose_format="eu
     ws, ptr, have = _place_workspace(None, nbytes, dev)
     _launch(dev, bwd, C.byref(d), C.c_void_p(ptr), have)
     return d_disps, d_poses
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the geometry-consistency term of SC-SfMLearner (include/sfmwarp_depth_consistency.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _depth_cons_desc(disps, src_disps, poses, K, pose_shape=(6,)):
+    """(descriptor with the inputs bound, the arrays it points at, B, n_src, [(h, w)], device) for depth_consistency_fwd / _bwd"""
+    S, n_src = len(disps), len(poses)
+    if len(src_disps) != S or not 1 <= S <= _lib.SFM_MAX_SCALES or not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("disps and src_disps need one entry per scale (1..%d), poses one per source (1..%d)"
+                        % (_lib.SFM_MAX_SCALES, _lib.SFM_MAX_SRC))
+    disps, src_disps, poses = _devs(disps, "disps", 4), _devs(src_disps, "src_disps", 4), _devs(poses, "poses", 1 + len(pose_shape))
+    K = _dev(K, "intrinsics", 4)
+    B, dev = disps[0].shape[0], disps[0].device
+    if tuple(K.shape) != (B, S, 3, 3):
+        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
+    hw = [tuple(t.shape[2:]) for t in disps]
+    for s, (h, w) in enumerate(hw):
+        if tuple(disps[s].shape) != (B, 1, h, w) or tuple(src_disps[s].shape) != (B, n_src, h, w):
+            raise TypeError("scale %d: expected disp (B,1,h,w) and src_disp %s, got %s and %s"
+                            % (s, (B, n_src, h, w), tuple(disps[s].shape), tuple(src_disps[s].shape)))
+    for i, t in enumerate(poses):
+        if tuple(t.shape) != (B,) + pose_shape:
+            raise TypeError("poses[%d] must be %s" % (i, _POSE_SHAPE_NAMES[pose_shape]))
+    _one_device(dev, disps + src_disps + poses + [K])
+    d = SfmDepthConsDesc()
+    d.B, d.n_src = B, n_src
+    _set_scales(d, hw)
+    d.intrinsics = K.data_ptr()
+    for field, arrays in ((d.disp, disps), (d.src_disp, src_disps), (d.pose, poses)):
+        _point(field, arrays)
+    return d, (disps, src_disps, poses, K), B, n_src, hw, dev
+
+
+def _conv_ref(conv):
+    return C.byref(conv) if conv is not None else None
+
+
+def depth_consistency_fwd(disps, src_disps, poses, K, want_valid=False, want_depths=False, pose_format="euler", invert=None,
+                          depth_affine=None):
+    """The geometry-consistency maps of every scale and source in ONE launch (sfm_depth_consistency_fwd): disps[s] (B,1,h,w) the
+    target's disparity, src_disps[s] (B,n_src,h,w) the sources' own, poses[i] (B,6), K (B,S,3,3) -> [diff_s (B,n_src,h,w)]:
+    |computed - projected| / (computed + projected) where the sample is in view, exactly 0 elsewhere -- computed the depth of the
+    target pixel's 3-D point in the source camera (clamped at 1e-3), projected the source's depth map sampled where it lands, at the
+    positions of `warp_pyramid_fwd` bit for bit.  With `want_valid` also [valid_s], with `want_depths` also [computed_s] and
+    [projected_s], all (B,n_src,h,w); returned as (diff, valid, computed, projected) without the lists that were not asked for.
+    pose_format, invert, depth_affine: the conventions of include/sfmwarp_pose.h (`pose_conv`), the affine map applied to both
+    disparities; "matrix" takes poses[i] (B,3,4)."""
+    conv = pose_conv(pose_format, invert, depth_affine, len(poses))
+    d, keep, B, n_src, hw, dev = _depth_cons_desc(disps, src_disps, poses, K, _pose_shape(conv))
+    shapes = [(B, n_src, h, w) for h, w in hw]
+    diff = _empty(shapes, dev)
+    valid = _empty(shapes, dev) if want_valid else None
+    computed, projected = (_empty(shapes, dev), _empty(shapes, dev)) if want_depths else (None, None)
+    for field, arrays in ((d.diff, diff), (d.valid, valid), (d.computed, computed), (d.projected, projected)):
+        _point(field, arrays or ())
+    _launch(dev, lib.sfm_depth_consistency_fwd, C.byref(d), _conv_ref(conv))
+    out = (diff,) + ((valid,) if want_valid else ()) + ((computed, projected) if want_depths else ())
+    return out if len(out) > 1 else diff
+
+
+def depth_consistency_bwd(disps, src_disps, poses, K, g_diff, want_d_src_disp=True, ws=None, pose_format="euler", invert=None,
+                          depth_affine=None):
+    """The backward of `depth_consistency_fwd` for the upstream gradients g_diff[s] (B,n_src,h,w): one launch over the pixels and a
+    small fold (sfm_depth_consistency_bwd) -> ([d_disp_s (B,1,h,w)], [d_pose_i (B,6)], [d_src_disp_s (B,n_src,h,w)] or None).
+    d_disp and d_pose: no atomics, the same bits on every call, whatever `ws` (the caller's workspace, or None for a fresh one)
+    held.  d_src_disp is scattered with float atomics (equal up to the order of the additions); want_d_src_disp=False launches the
+    kernel without the scatter.  Under pose_format="matrix" d_pose_i is (B,3,4): the gradient of the matrix itself."""
+    conv = pose_conv(pose_format, invert, depth_affine, len(poses))
+    d, keep, B, n_src, hw, dev = _depth_cons_desc(disps, src_disps, poses, K, _pose_shape(conv))
+    if len(g_diff) != len(hw):
+        raise TypeError("g_diff needs one entry per scale")
+    g_diff = _devs(g_diff, "g_diff", 4)
+    for s, (h, w) in enumerate(hw):
+        if tuple(g_diff[s].shape) != (B, n_src, h, w) or g_diff[s].device != dev:
+            raise TypeError("g_diff[%d] must be (B,n_src,h,w) = %s on %s" % (s, (B, n_src, h, w), dev))
+    d_disps = _empty([(B, 1, h, w) for h, w in hw], dev)
+    d_poses = _empty([(B,) + _pose_shape(conv)] * n_src, dev)
+    d_src_disps = _empty([(B, n_src, h, w) for h, w in hw], dev) if want_d_src_disp else None      # (the call clears them itself)
+    for field, arrays in ((d.g_diff, g_diff), (d.d_disp, d_disps), (d.d_pose, d_poses), (d.d_src_disp, d_src_disps or ())):
+        _point(field, arrays)
+    nbytes = lib.sfm_depth_consistency_bwd_workspace_bytes(C.byref(d), _conv_ref(conv))
+    if nbytes == 0:
+        check(lib.sfm_depth_consistency_bwd(C.byref(d), _conv_ref(conv), None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid depth consistency descriptor")
+    ws, ptr, have = _place_workspace(ws, nbytes, dev)
+    _launch(dev, lib.sfm_depth_consistency_bwd, C.byref(d), _conv_ref(conv), C.c_void_p(ptr), have)
+    return d_disps, d_poses, d_src_disps
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

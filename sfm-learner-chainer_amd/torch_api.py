@@ -47,7 +47,8 @@ from ._lib import SfmLossDesc, lib
 
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
            "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error",
-           "min_reprojection", "min_reprojection_loss", "disparity_smoothness", "warp_full_res", "pose_matrix"]
+           "min_reprojection", "min_reprojection_loss", "disparity_smoothness", "warp_full_res", "pose_matrix",
+           "depth_consistency"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -669,6 +670,91 @@ def warp_pyramid(src_imgs, intrinsics, pred_disps, pred_poses, *, return_valid=F
     S = len(disps)
     out = _WarpPyramid.apply(src.view(B, 3 * n_src, H, W), K, S, bool(return_valid), pc, *disps, *poses)
     return (list(out[:S]), list(out[S:])) if return_valid else list(out)
+
+
+class _DepthConsistency(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, K, S, want_valid, want_depths, pc, *arrays):
+        disps, src_disps, poses = list(arrays[:S]), list(arrays[S:2 * S]), list(arrays[2 * S:])
+        out = ops.depth_consistency_fwd(disps, src_disps, poses, K, want_valid, want_depths, **_pose_kw(pc))
+        out = (out,) if not (want_valid or want_depths) else out
+        ctx.save_for_backward(K, *disps, *src_disps, *poses)
+        ctx.S, ctx.pc = S, pc
+        flat = tuple(t for group in out for t in group)
+        ctx.mark_non_differentiable(*flat[S:])
+        ctx.set_materialize_grads(False)              # (a scale the caller's loss does not use: one zero fill here, not one per output)
+        return flat
+
+    @staticmethod
+    def backward(ctx, *grads):
+        S = ctx.S
+        K, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        disps, src_disps, poses = list(saved[:S]), list(saved[S:2 * S]), list(saved[2 * S:])
+        g = [torch.zeros_like(sd) if gr is None else gr.to(torch.float32).contiguous() for gr, sd in zip(grads[:S], src_disps)]
+        want = any(ctx.needs_input_grad[5 + S:5 + 2 * S])      # src_disps that do not require grad: the kernel without the scatter
+        d_disps, d_poses, d_src = ops.depth_consistency_bwd(disps, src_disps, poses, K, g, want_d_src_disp=want, **_pose_kw(ctx.pc))
+        return (None,) * 5 + tuple(d_disps) + (tuple(d_src) if want else (None,) * S) + tuple(d_poses)
+
+
+def depth_consistency(pred_disps, src_disps, intrinsics, pred_poses, *, return_valid=False, return_depths=False, pose_format="euler",
+                      invert=None, depth_range=None):
+    """The geometry-consistency term of SC-SfMLearner (Bian et al., NeurIPS 2019: inverse_warp2 and compute_pairwise_loss) for every
+    scale and source of a step, as ONE autograd node on this library's warp:
+
+      diff = |computed - projected| / (computed + projected)
+
+    where computed is the depth of the target pixel's 3-D point seen from the source camera (clamped at 1e-3) and projected the
+    source frame's own predicted depth, sampled bilinearly where that point lands -- at the positions of `warp_pyramid` with the same
+    arguments, bit for bit.  A pixel whose sample is not in view gets exactly 0.
+
+    pred_disps: S tensors (B,1,h_s,w_s), the target frame's disparities (any sizes of at least 3x3 per scale);
+    src_disps: S tensors (B,n_src,h_s,w_s), the disparity the SAME network predicts for each source frame;
+    intrinsics (B,S,3,3) float32: a constant -- if it requires grad this raises TypeError, as in `warp_pyramid`;
+    pred_poses: n_src tensors (B,6) or one packed (B,6*n_src) tensor.  Predictions are float32, bfloat16 or float16 on a ROCm
+      device, computed in float32, each gradient returned in its input's dtype.  Gradients flow to pred_disps, src_disps and
+      pred_poses; src_disps that do not require grad (detached, or under no_grad) skip the scatter that forms their gradient.
+
+    Returns the list of S tensors diff_s (B,n_src,h_s,w_s), each in [0, 1) for positive disparities.  With `return_valid` also the S
+    masks (1.0 where the sample passes both strict in-view tests, else 0.0), with `return_depths` also the S computed and the S
+    projected depths: (diff, valid, computed, projected) without the lists not asked for; only diff is differentiable.
+
+    It adds no reduction.  SC-SfMLearner's geometry loss and its self-discovered mask are two aten lines on the result:
+      geometry = sum((d * v).sum() / v.sum().clamp(min=1) for d, v in zip(diff, valid))
+      weighted = [err_s * (1 - d) for err_s, d in zip(photometric_error_maps, diff)]
+
+    One launch forward; backward one launch over the pixels plus a small fold, whatever S and n_src are.  Nothing reads a device
+    value on the host: it runs under torch.cuda.graph capture.  pose_format, invert and depth_range are those of `warp_pyramid`;
+    depth_range acts on both disparities."""
+    pc = _pose_conv_args(None, pose_format, invert, depth_range)
+    if isinstance(pred_disps, torch.Tensor) or isinstance(src_disps, torch.Tensor):
+        raise TypeError("pred_disps and src_disps are lists with one tensor per scale")
+    S = len(pred_disps)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES or len(src_disps) != S:
+        raise TypeError("1..%d scales, and as many src_disps as pred_disps: got %d and %d" % (_lib.SFM_MAX_SCALES, S, len(src_disps)))
+    disps = [_dev_float(t, "pred_disps[%d]" % s, 4) for s, t in enumerate(pred_disps)]
+    srcs = [_dev_float(t, "src_disps[%d]" % s, 4) for s, t in enumerate(src_disps)]
+    B, n_src = srcs[0].shape[:2]
+    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d sources, got %d" % (_lib.SFM_MAX_SRC, n_src))
+    if pc[1] is not None and len(pc[1]) != n_src:
+        raise ValueError("invert needs one boolean per source (%d), got %d" % (n_src, len(pc[1])))
+    for s, (t, u) in enumerate(zip(disps, srcs)):
+        h, w = t.shape[2:]
+        if tuple(t.shape) != (B, 1, h, w) or tuple(u.shape) != (B, n_src, h, w):
+            raise TypeError("scale %d: pred_disps must be (B,1,h,w) and src_disps (B,n_src,h,w) = %s, got %s and %s"
+                            % (s, (B, n_src, h, w), tuple(t.shape), tuple(u.shape)))
+    K = ops._dev(intrinsics, "intrinsics", 4)
+    if tuple(K.shape) != (B, S, 3, 3):
+        raise TypeError("intrinsics must be (B,%d,3,3), got %s" % (S, tuple(K.shape)))
+    if K.requires_grad:
+        raise TypeError("depth_consistency does not differentiate the intrinsics: detach them")
+    poses = _poses(pred_poses, B, n_src, pose_format)
+    for t in [K] + srcs + poses:
+        if t.device != disps[0].device:
+            raise TypeError("every array must live on %s, one is on %s" % (disps[0].device, t.device))
+    out = _DepthConsistency.apply(K, S, bool(return_valid), bool(return_depths), pc, *disps, *srcs, *poses)
+    groups = [list(out[k:k + S]) for k in range(0, len(out), S)]
+    return tuple(groups) if len(groups) > 1 else groups[0]
 
 
 class _WarpFullRes(torch.autograd.Function):
