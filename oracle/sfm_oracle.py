@@ -376,9 +376,9 @@ def projective_inverse_warp(imgs, depthes, poses, K, dtype=np.float32, return_au
     return out
 
 
-def projective_inverse_warp_backward(imgs, depthes, poses, K, g_out, dtype=np.float32, want_gimgs=False):
+def projective_inverse_warp_backward(imgs, depthes, poses, K, g_out, dtype=np.float32, want_gimgs=False, want_gPm=False):
     """Backward of projective_inverse_warp for an upstream gradient g_out (N,3,H,W).
-    -> (g_depthes (N,3,P), g_poses (N,6), g_imgs | None)"""
+    -> (g_depthes (N,3,P), g_poses (N,6), g_imgs | None), with want_gPm also gPm (N,4,4), the gradient of Pm = K4 . T"""
     imgs = np.asarray(imgs, dtype=dtype)
     depthes = np.asarray(depthes, dtype=dtype)
     N, _, H, W = imgs.shape
@@ -397,6 +397,8 @@ def projective_inverse_warp_backward(imgs, depthes, poses, K, g_out, dtype=np.fl
     gcam = _bmm(np.transpose(aux["Pm"], (0, 2, 1)), gq)                    # (N,4,P)
     g_depthes = gcam[:, :3] * aux["ray"]
     g_poses = proj_tgt_to_src_backward(poses, K, gPm, dtype)
+    if want_gPm:
+        return g_depthes.astype(dtype), g_poses, gimgs, gPm
     return g_depthes.astype(dtype), g_poses, gimgs
 
 

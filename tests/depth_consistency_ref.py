@@ -74,13 +74,14 @@ def _sign(x):
 
 def reference(d, dtype, g_diff=None, backward=True):
     """The header in `dtype` on the float32 inputs d.  -> dict of per-scale lists diff, valid, computed, projected, q2, margin,
-    cell_margin (B,n_src,h,w) and, with backward, d_disps (B,1,h,w), d_src_disps (B,n_src,h,w), d_poses[i] (B,6) for the upstream
-    g_diff (default: d["g_diff"])."""
+    cell_margin (B,n_src,h,w) and, with backward, d_disps (B,1,h,w), d_src_disps (B,n_src,h,w), d_poses[i] (B,6) and d_T[i] (B,3,4): the
+    gradient of T = [R|t] itself, K^T . gPm summed over the scales (what pose_format="matrix" returns), for the upstream g_diff
+    (default: d["g_diff"])."""
     B, n_src, S = d["B"], d["n_src"], d["n_scales"]
     g_diff = d["g_diff"] if g_diff is None else g_diff
     keys = ("diff", "valid", "computed", "projected", "q2", "margin", "cell_margin")
     out = {k: [] for k in keys}
-    out.update(d_disps=[], d_src_disps=[], d_poses=[np.zeros((B, 6), dtype) for _ in range(n_src)])
+    out.update(d_disps=[], d_src_disps=[], d_poses=[np.zeros((B, 6), dtype) for _ in range(n_src)], d_T=[np.zeros((B, 3, 4), dtype) for _ in range(n_src)])
     two, clamp = dtype(2), dtype(CLAMP)
     for s in range(S):
         disp = np.asarray(d["disps"][s], dtype)
@@ -116,8 +117,8 @@ def reference(d, dtype, g_diff=None, backward=True):
                 f_p = -(sgn * ((two * c) / dd))
                 g_c = np.where(ok, g * f_c, dtype(0))
                 g_p = np.where(ok, g * f_p, dtype(0))
-            g_depthes, g_pose, g_img = O.projective_inverse_warp_backward(img, depthes, d["poses"][i], K, g_p.reshape(B, 1, h, w), dtype,
-                                                                          want_gimgs=True)
+            g_depthes, g_pose, g_img, gPm_p = O.projective_inverse_warp_backward(img, depthes, d["poses"][i], K, g_p.reshape(B, 1, h, w), dtype,
+                                                                                 want_gimgs=True, want_gPm=True)
             # the q2 path: q2 -> clamp -> computed
             gq2 = np.where(q2 > clamp, g_c, dtype(0))                                   # (B,P)
             gPm = np.zeros((B, 4, 4), dtype)
@@ -125,6 +126,7 @@ def reference(d, dtype, g_diff=None, backward=True):
             gcam = aux["Pm"][:, 2, :3][:, :, None] * gq2[:, None, :]                   # gcam += Pm[2, :3]^T g_c
             g_depth = g_depth + (g_depthes.sum(axis=1) + (gcam * aux["ray"]).sum(axis=1))
             out["d_poses"][i] = out["d_poses"][i] + (g_pose + O.proj_tgt_to_src_backward(d["poses"][i], K, gPm, dtype))
+            out["d_T"][i] = out["d_T"][i] + O._bmm(np.transpose(O._K4(K, dtype), (0, 2, 1)), gPm_p + gPm)[:, :3]
             d_src.append((-g_img / (sd_src * sd_src))[:, 0])
         for k in keys:
             out[k].append(np.stack(per[k], axis=1))
@@ -142,12 +144,16 @@ def references(shape, seed):
 
 
 def torch_opinion(d, g_diff=None):
-    """The same term in torch float64 on the CPU, gradients by autograd.  -> dict with diff, d_disps, d_src_disps, d_poses as NumPy"""
+    """The same term in torch float64 on the CPU, gradients by autograd.  -> dict with diff, d_disps, d_src_disps, d_poses and d_T (the
+    gradient of every entry of T = [R|t]) as NumPy"""
     g_diff = d["g_diff"] if g_diff is None else g_diff
     t64 = lambda a: torch.from_numpy(np.asarray(a, F64))
     disps = [t64(a).requires_grad_() for a in d["disps"]]
     srcs = [t64(a).requires_grad_() for a in d["src_disps"]]
     poses = [t64(a).requires_grad_() for a in d["poses"]]
+    Ts = [PR.pose_matrix_t(pose, "euler") for pose in poses]                                                   # (B,3,4)
+    for T in Ts:
+        T.retain_grad()
     Ks = t64(d["intrinsics"])
     diffs, total = [], 0.0
     for s, (disp, src) in enumerate(zip(disps, srcs)):
@@ -157,8 +163,8 @@ def torch_opinion(d, g_diff=None):
         pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(h * w, dtype=torch.float64)], 0)       # (3,P)
         cam = (1.0 / disp).reshape(B, 1, h * w) * (torch.linalg.inv(K) @ pix)                                  # (B,3,P)
         per = []
-        for i, pose in enumerate(poses):
-            Pm = K @ PR.pose_matrix_t(pose, "euler")                                                           # (B,3,4)
+        for i, T in enumerate(Ts):
+            Pm = K @ T                                                                                         # (B,3,4)
             q = Pm[:, :, :3] @ cam + Pm[:, :, 3:]
             z = q[:, 2] + 1e-10
             xn = (q[:, 0] / z) / ((w - 1) / 2.0) - 1.0
@@ -176,7 +182,7 @@ def torch_opinion(d, g_diff=None):
         total = total + (diff * t64(g_diff[s])).sum()
     total.backward()
     return dict(diff=[t.detach().numpy() for t in diffs], d_disps=[t.grad.numpy() for t in disps],
-                d_src_disps=[t.grad.numpy() for t in srcs], d_poses=[t.grad.numpy() for t in poses])
+                d_src_disps=[t.grad.numpy() for t in srcs], d_poses=[t.grad.numpy() for t in poses], d_T=[T.grad.numpy() for T in Ts])
 
 
 def knife_of(ref):

@@ -43,7 +43,7 @@ def test_the_two_float64_statements_agree(case):
     """NumPy on the oracle's warp with a hand-derived backward against torch autograd through grid_sample, inv and matmul"""
     o64, _ = R.references(*case)
     t = R.torch_opinion(R.inputs(*case))
-    for key in ("diff",) + R.GRADS:
+    for key in ("diff",) + R.GRADS + ("d_T",):      # d_T: all 12 entries of the gradient of T = [R|t], what pose_format="matrix" returns
         assert len(o64[key]) == len(t[key])
         for k, (a, b) in enumerate(zip(o64[key], t[key])):
             top = np.abs(a).max()

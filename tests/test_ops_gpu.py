@@ -77,7 +77,8 @@ def warp_inputs(synth, shape, texture, depth_rows, kind=None):
 
 
 def check_warp_fwd_bwd(ops, dev, inp, shape, texture, depth_rows):
-    """the body of test_projective_inverse_warp_fwd_bwd on the inputs `inp` (warp_inputs)"""
+    """the body of test_projective_inverse_warp_fwd_bwd on the inputs `inp` (warp_inputs).  These inputs have knife pixels;
+    tests/test_warp_exact_gpu.py holds the same operator to float64, every element, on inputs that have none."""
     N, C, H, W = shape
     imgs, depthes, dev_depth, pose, K, rng = (inp[k] for k in ("imgs", "depthes", "dev_depth", "pose", "K", "rng"))
     want, aux = O.projective_inverse_warp(imgs, depthes, pose, K, return_aux=True)
