@@ -591,7 +591,7 @@ class SfmLossResult(dict):
 def sfm_loss(tgt_pyr, src_pyr, intrinsics, disps, poses, masks=None, *,
              smooth_reg=0.0, exp_reg=0.0, ssim_rate=0.0, smooth_mode="second_order",
              n_scales=None, dtype=np.float32, backward=False, want_d_src=False,
-             keep_warped=False, norm_batch=None):
+             keep_warped=False, norm_batch=None, want_d_proj=False):
     """SFMLearner.__call__ from the pyramid onwards (base_model.py:69-124).
 
     tgt_pyr[s]   (B,3,h_s,w_s)     -- curr_tgt_img  (:71)
@@ -603,7 +603,8 @@ def sfm_loss(tgt_pyr, src_pyr, intrinsics, disps, poses, masks=None, *,
     norm_batch   batch size used in the means (for a batch shard: the GLOBAL batch); default B.
 
     backward=True also returns d_disps[s], d_poses[i], d_masks[s] (and d_src[s] if asked)
-    for an upstream gradient of 1 on total_loss.
+    for an upstream gradient of 1 on total_loss; with want_d_proj also d_proj (B,S,n,3,4) =
+    dL/dPm: rows 0..2 of the gPm of projective_inverse_warp_backward for each (scale, source).
     """
     S = len(disps) if n_scales is None else n_scales
     B = tgt_pyr[0].shape[0]
@@ -617,6 +618,7 @@ def sfm_loss(tgt_pyr, src_pyr, intrinsics, disps, poses, masks=None, *,
     d_poses = [np.zeros((B, 6), dtype=dtype) for _ in range(n_src)]
     d_masks = [np.zeros_like(np.asarray(masks[s], dtype=dtype)) for s in range(S)] if do_exp else None
     d_srcs = [np.zeros_like(np.asarray(src_pyr[s], dtype=dtype)) for s in range(S)] if want_d_src else None
+    d_proj = np.zeros((B, S, n_src, 3, 4), dtype=dtype) if want_d_proj else None
     warped_all, margin_all, cell_all, abs_all, clip_all, uv_all, zero_all = [], [], [], [], [], [], []
 
     for s in range(S):
@@ -678,8 +680,10 @@ def sfm_loss(tgt_pyr, src_pyr, intrinsics, disps, poses, masks=None, *,
                         g_se = alpha * (dtype(1) - mb.astype(dtype)) / cnt
                         g_proj = g_proj + compute_ssim_backward(proj, tgt, g_se, dtype)
             if backward:
-                g_dep, g_pose, g_img = projective_inverse_warp_backward(
-                    img, depthes, poses[i], K, g_proj, dtype, want_gimgs=want_d_src)
+                g_dep, g_pose, g_img, *g_pm = projective_inverse_warp_backward(
+                    img, depthes, poses[i], K, g_proj, dtype, want_gimgs=want_d_src, want_gPm=want_d_proj)
+                if want_d_proj:
+                    d_proj[:, s, i] = g_pm[0][:, :3]
                 gD = g_dep.sum(axis=1).reshape(B, 1, h, w)                     # broadcast_to backward
                 d_disps[s] += -gD / (disp * disp)                              # 1/d backward (:60)
                 d_poses[i] += g_pose
@@ -708,6 +712,8 @@ def sfm_loss(tgt_pyr, src_pyr, intrinsics, disps, poses, masks=None, *,
                exp_loss=exp_loss, ssim_loss=ssim_loss)
     if backward:
         res.update(d_disps=d_disps, d_poses=d_poses, d_masks=d_masks, d_srcs=d_srcs)
+        if want_d_proj:
+            res.update(d_proj=d_proj)
     if keep_warped:
         res.update(warped=warped_all, margin=margin_all, cell_margin=cell_all, abs_margin=abs_all, abs_zero=zero_all, clip_margin=clip_all, uv=uv_all)
     return res

@@ -18,6 +18,7 @@ import importlib
 
 import numpy as np
 
+import cameras
 from oracle import sfm_oracle as O
 from oracle.parity import knife_mask
 from test_loss_gpu import CONFIGS, KEYS, cell_width_from_position_bound
@@ -61,8 +62,9 @@ YARDSTICK_MAX = 1e-4        # max|o32 - o64| / max|o64| of every gradient array:
 SEARCH_CONFIG = "ssim_smooth"   # the configuration that has every knife class, the clip of (1-SSIM)/2 included
 
 
-def make_inputs(shape, seed):
-    """synth.make_inputs(seam="shift", with_masks=True) with the images rescaled (see the module docstring); float32 throughout."""
+def make_inputs(shape, seed, kind=None):
+    """synth.make_inputs(seam="shift", with_masks=True) with the images rescaled (see the module docstring); float32 throughout.
+    kind: the intrinsics replaced by tests/cameras.py's cameras of that kind, drawn with the seed 1000 + seed (None: synth's own)."""
     B, H, W, n_src, n_scales = shape
     d = synth.make_inputs(B=B, H=H, W=W, n_src=n_src, n_scales=n_scales, seed=seed, with_masks=True, seam="shift")
     sign = np.where(np.random.RandomState(1000 + seed).randint(0, 2, size=(B, n_src, 3, 1, 1)) > 0, F32(1), F32(-1))
@@ -70,7 +72,7 @@ def make_inputs(shape, seed):
     src = (F32(0.3) * d["src"] + F32(0.45) * sign).astype(F32)
     d.update(tgt=tgt, src=src, tgt_pyr=synth.image_pyramid(tgt, n_scales),
              src_pyr=synth.image_pyramid(src.reshape(B, 3 * n_src, H, W), n_scales))
-    return d
+    return cameras.with_cameras(d, kind, 1000 + seed)
 
 
 def oracle(d, cfg, dtype, backward=True, **weights):
@@ -185,10 +187,10 @@ def yardsticks(o64, o32, cfg):
     return out
 
 
-def failed_conditions(shape, seed, cfg_name=SEARCH_CONFIG, with_yardstick=True):
+def failed_conditions(shape, seed, cfg_name=SEARCH_CONFIG, with_yardstick=True, kind=None):
     """The conditions of tests/test_knife_free_cpu.py that (shape, seed) misses under one configuration, as a list of strings
-    (empty: knife-free).  The cheap ones first; the yardstick needs the two backward passes."""
-    d, cfg = make_inputs(shape, seed), CONFIGS[cfg_name]
+    (empty: knife-free).  The cheap ones first; the yardstick needs the two backward passes.  kind: as make_inputs."""
+    d, cfg = make_inputs(shape, seed, kind), CONFIGS[cfg_name]
     bad = []
     for mode in ("second_order", "edge_aware"):
         for dtype in (F64, F32):

@@ -6,7 +6,8 @@ Three gradient paths end in a kernel in which ONE wave adds a sample's partial s
     proj_bwd_kernel        csrc/sfm_loss.hip           tiles per (sample, scale, source)              d_proj, d_intrinsics of sfm_loss_proj_bwd
 A case of at most 64 partials never takes the second trip of that loop, and would pass whatever a later trip did.  The cases that
 go further are  tests/test_warp_pyramid_gpu.py::FOLD_CASES (65 blocks),  tests/test_intrinsics_grad_gpu.py::WARP_LARGE (65 and 208
-blocks)  and  tests/intrinsics_grad.py::LARGE_SHAPES / LARGE_FAMILY_CASES (66, 128 and 224 tiles).  A block size or a plan heuristic
+blocks),  tests/intrinsics_grad.py::LARGE_SHAPES / LARGE_FAMILY_CASES (66, 128 and 224 tiles)  and, on textured inputs,
+tests/intrinsics_exact_ref.py::FOLD_SHAPE (65 tiles).  A block size or a plan heuristic
 that changes could take them back inside the first trip without any of those tests failing; this module fails instead.
 
   1. the block sizes, read from the sources, give more than 64 blocks at scale 0 of every such warp case;
@@ -24,8 +25,9 @@ import re
 import numpy as np
 import pytest
 
+import intrinsics_exact_ref as XR
 import intrinsics_grad as IG
-import test_intrinsics_grad_gpu as KG       # (importing a GPU module's cases launches nothing)
+import test_intrinsics_grad_gpu as KG      # (importing a GPU module's cases launches nothing)
 import test_warp_pyramid_gpu as WP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,6 +97,16 @@ def test_the_new_fused_cases_have_more_than_64_tiles_in_the_expected_family():
     assert [IG.LARGE_TILES[s][0] - WAVE for s in IG.LARGE_SHAPES] == [2, 64, 160] and IG.LARGE_TILES[IG.LARGE_SHAPES[2]][1] == WAVE
     # the small shapes stay what their docstrings say: at most 6 tiles per scale
     assert max(max(IG.host_plan(s, "ssim_smooth")[0]) for s in IG.SHAPES) <= 6
+    # the textured, knife-free frame of tests/intrinsics_exact_ref.py: 260 rows in 4-row chunks, one strip -- 65 tiles, one lane goes
+    # round a second time -- in every launch tests/test_intrinsics_exact_gpu.py makes of it
+    assert XR.FOLD_SHAPE == (1, 260, 20, 2, 1) and XR.FOLD_TILES == [65] and XR.FOLD_SHAPE in XR.CASES
+    for mode in XR.CONFIGS:
+        for projection in ("reference_order", "fast"):
+            for layout in ("planar", "hwc"):
+                for want_d_src in (False, True):
+                    for loss in (1, 0):
+                        tiles = IG.host_plan(XR.FOLD_SHAPE, mode, layout, projection, want_d_src, grad=1, loss=loss)[0]
+                        assert tiles == XR.FOLD_TILES and max(tiles) > WAVE, (mode, projection, layout, want_d_src, loss, tiles)
 
 
 def test_the_pose_tolerance_follows_the_documented_rule():

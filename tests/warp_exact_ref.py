@@ -22,6 +22,7 @@ import importlib
 import numpy as np
 import torch
 
+import cameras
 import depth_consistency_ref as DR
 import pose_conv_ref as PR
 from depth_consistency_ref import CELL_MARGIN, VALID_SHARE, VIEW_MARGIN, YARDSTICK_MAX, case_id  # noqa: F401  (the conditions' numbers)
@@ -42,6 +43,8 @@ SETTINGS = {
     "invert": dict(fmt="euler", invert=True, affine=False),
     "affine": dict(fmt="euler", invert=False, affine=True),
     "matrix": dict(fmt="matrix", invert=False, affine=False),          # a 3x4 that is not rigid
+    # the default conventions under tests/cameras.py's general cameras (skew, a bottom row, per-scale rows), seed 1000 + seed
+    "general_cameras": dict(fmt="euler", invert=False, affine=False, cameras="general"),
 }
 
 # (B, H, W, n_src, n_scales) -> seeds
@@ -56,11 +59,14 @@ CONV_CASES = {
 ALONE_CASES = {"axis_angle": ((1, 24, 40, 3, 3), 9), "invert": ((1, 24, 40, 3, 3), 25), "affine": ((1, 24, 40, 3, 3), 4)}
 # the first two seeds that `search((1, 24, 40, 3, 3), "matrix", 0, 40)` finds
 MATRIX_CASES = {(1, 24, 40, 3, 3): (16, 20)}
+# the first two seeds that `search((2, 13, 21, 2, 1), "general_cameras", 0, 40)` finds: for sfm_warp_intrinsics_bwd
+# (tests/intrinsics_exact_ref.py), every entry of K and every shortcut through it
+GENERAL_CASES = {(2, 13, 21, 2, 1): (6, 15)}
 
 
 # The operator's three depth rows are scaled by factors in (0.98, 1.02) (tests/test_ops_gpu.py::warp_inputs): that moves every sample, so
 # the draw belongs to the case.  (shape, seed) -> the first draw k >= 0 that `search_rows` finds knife-free (0 where not listed); the
-# factors come from RandomState(7200 + 100 k + seed).
+# factors come from RandomState(7200 + 100 k + seed).  (A case of another setting would be listed as (shape, seed, setting).)
 ROWS_DRAWS = {((2, 13, 21, 2, 1), 1): 4, ((1, 24, 40, 3, 3), 6): 1, ((1, 24, 40, 3, 3), 19): 6}
 
 
@@ -94,7 +100,7 @@ def make_inputs(shape, seed, setting="default", rows_draw=None):
     g = [np.ascontiguousarray(rng.standard_normal(size=(B, n_src, 3) + t.shape[2:]), dtype=F32) for t in d["disps"]]
     g_op = np.ascontiguousarray(rng.standard_normal(size=(B, n_src, 5, H, W)), dtype=F32)
     # tests/test_ops_gpu.py::warp_inputs' perturbation of the three depth rows, from a generator of its own
-    k = ROWS_DRAWS.get((shape, seed), 0) if rows_draw is None else rows_draw
+    k = ROWS_DRAWS.get((shape, seed) if setting == "default" else (shape, seed, setting), 0) if rows_draw is None else rows_draw
     rows = np.random.RandomState(7200 + 100 * k + seed).uniform(0.98, 1.02, size=(B, 3, 1)).astype(F32)
     disps, poses, affine = d["disps"], d["poses"], None
     if conf["affine"]:
@@ -103,7 +109,8 @@ def make_inputs(shape, seed, setting="default", rows_draw=None):
     if setting == "matrix":
         u = np.random.RandomState(8000 + seed)
         poses = [(PR.pose_matrix(p, "axis_angle", False, F64) * (1 + NONRIGID * u.uniform(-1, 1, size=(B, 3, 4)))).astype(F32) for p in poses]
-    return dict(src_pyr=d["src_pyr"], tgt_pyr=d["tgt_pyr"], disps=disps, poses=poses, intrinsics=d["intrinsics"], g=g, g_op=g_op, rows=rows,
+    intrinsics = cameras.cameras(d, conf["cameras"], 1000 + seed) if conf.get("cameras") else d["intrinsics"]
+    return dict(src_pyr=d["src_pyr"], tgt_pyr=d["tgt_pyr"], disps=disps, poses=poses, intrinsics=intrinsics, g=g, g_op=g_op, rows=rows,
                 fmt=conf["fmt"], invert=[bool(conf["invert"]) and i % 2 == 0 for i in range(n_src)], affine=affine,
                 B=B, n_src=n_src, n_scales=n_scales)
 
@@ -317,7 +324,7 @@ def yardsticks(o64, o32, keys=ARRAYS):
 
 def failed_conditions(shape, seed, setting="default", with_yardstick=True, rows_draw=None):
     """the conditions of tests/test_warp_exact_cpu.py that (shape, seed) misses under `setting`, as strings (empty: knife-free).  The
-    default setting includes the operator's three-row form on every source (its depth rows move the samples)."""
+    default setting and "general_cameras" include the operator's three-row form on every source (its depth rows move the samples)."""
     d = make_inputs(shape, seed, setting, rows_draw)
     fwd = reference(d, F64, backward=False), reference(d, F32, backward=False)
     bad = ["%d knife pairs at scale %d" % (int(m.sum()), s) for s, m in enumerate(knife(d, fwd)) if m.any()]
@@ -329,7 +336,7 @@ def failed_conditions(shape, seed, setting="default", with_yardstick=True, rows_
             if not VALID_SHARE[0] <= share <= VALID_SHARE[1]:
                 bad.append("valid share %.3f at scale %d, source %d" % (share, s, i))
     ops = []
-    if setting == "default":
+    if setting in ("default", "general_cameras"):
         for i in range(d["n_src"]):
             pair = operator_reference(d, F64, 3, 3, i), operator_reference(d, F32, 3, 3, i)
             ops.append(pair)
