@@ -29,6 +29,47 @@
  *     A NaN anywhere in an image makes the loss NaN, as in the reference.  Image values are taken to be zero or NORMAL
  *     floats: the zero mask of models/base_model.py:96 is formed as clamp(max_c |I^_c| * 2^127, 0, 1), which is exactly 0 / 1 for those
  *     and a fraction of 1 for a pixel whose three warped channels are all subnormal (|.| < 1.2e-38; uint8 / 127.5 - 1 has none);
+ *   - NON-FINITE AND DEGENERATE INPUTS (a disparity, depth, pose, intrinsics or grid entry that is NaN, +-inf, 0, negative,
+ *     denormal or 1e+-30; an upstream gradient that is NaN or inf).  Every entry point of this header and of sfmwarp_pose.h,
+ *     sfmwarp_full_res.h, sfmwarp_depth_consistency.h terminates, returns 0 and reads and writes inside its arrays on them
+ *     (profiles/hostile_inputs_audit.md lists every place where such a number becomes an address, with its guard); what one sample
+ *     holds never changes a bit of another sample's outputs, and a hostile disparity changes the forward outputs of its own pixel
+ *     only (sfm_warp_full_res_*: of the pixels whose upsampling reads it); every call gives the same bits twice (the outputs
+ *     accumulated with atomics: the same finite / inf / NaN pattern).  tests/test_hostile_inputs_gpu.py pins all of it.  The values:
+ *       * sfm_sampler_*, and the sampler inside sfm_warp_*, sfm_warp_pyramid_*, sfm_warp_full_res_*, sfm_depth_consistency_*: the
+ *         padded position is clamped with fminf(fmaxf(.)), so a NaN grid coordinate is clamped to the first column / row of the zero
+ *         frame -- the sample is exactly 0 and its ggrid component 0 where the reference's formula (np.clip keeps a NaN) gives NaN; a
+ *         position that is +-inf or beyond the int range is clipped to the frame like any position outside, as in the reference.
+ *         sfm_sampler_interp_*: a NaN coordinate takes the first column / row with NaN weights (y, and the ggrid formed with them, NaN).
+ *       * operator path (sfm_warp_*, sfm_warp_pyramid_*, sfm_warp_full_res_*, sfm_depth_consistency_*): a pixel whose projected
+ *         position is NaN (a NaN or zero disparity, a NaN depth, a NaN or infinite translation, a NaN or singular K) has the value 0
+ *         and valid 0, but its dL/dq = 0 / z is NaN: d_depth / d_disp of that pixel and ALL of that sample's d_pose, d_T and d_K for
+ *         that source are NaN.  Zero disparity is depth +inf: out of view (a NaN position wherever the ray has a zero component).
+ *       * Euler poses everywhere (sfm_pose_proj_*, sfm_pose_mat_*, the warps, the fused loss): the clip of transform.py:23 is
+ *         fminf(fmaxf(r, -pi), pi): a NaN Euler angle is read as -pi, and its own gradient is 0 (the clip's backward); an angle of
+ *         +-inf or 1e30 is +-pi, as in the reference.  sfm_pose_proj_fwd: row 3 of the output is written as (0, 0, 0, 1) whatever the
+ *         pose (the reference's 0 x NaN there is NaN).  An axis-angle vector with a NaN entry gives a NaN matrix, as the formula does.
+ *       * fused loss (sfm_loss_*, sfm_step_*), both projections: a sample whose position is not finite is NOT IN VIEW -- no tap of
+ *         it is addressed, it receives and contributes no gradient through the sampler.  If the position is NaN, in the planar layout
+ *         its warped value is exactly 0; in the pixel-interleaved layout it is NaN (the zero taps are blended with NaN fractions), and
+ *         then pixel_loss and total_loss are NaN (ssim_loss is not: the zero mask counts the pixel as masked) -- the planar layout
+ *         swallows it, as the clamped sampler does.  The kernel families and entry points of one layout and projection agree on the
+ *         class (finite / inf / NaN) of every output element and on the exactly-zero set of warped; so do the two projections, except
+ *         for an infinite disparity (below).  d_disp of the
+ *         pixel, and d_pose of every source of that sample, are NaN in both layouts; beyond that the class of the gradients around a
+ *         hostile disparity is a property of each formula (the sign of a NaN difference is taken as +-1, the SSIM window spreads a NaN
+ *         warped value in the pixel-interleaved layout): the launches of a layout agree on it, the reference's formula need not.
+ *         A non-finite POSE entry is NOT reported by the fused loss, where the reference's loss and d_pose are NaN: a NaN angle is
+ *         -pi to every kernel -- every output is finite, the angle's own gradient 0 --, and a NaN or infinite translation puts every
+ *         pixel of that source at a NaN position (planar: the source contributes exact zeros and the scalars stay finite;
+ *         pixel-interleaved: NaN as above; d_disp of that sample is NaN in both).
+ *         an infinite disparity is depth 0 in the default projection and a NaN depth under SFM_PROJECTION_REFERENCE_ORDER (its 1 / disp
+ *         carries a residual correction: 0 x inf); the smoothness terms of a stencil that holds an infinite disparity are NaN
+ *         (inf - inf) where the reference's order of differences gives +inf.
+ *       * a singular or NaN K makes K^-1 non-finite: every pixel of that (sample, scale) is as above.
+ *     WHAT A CALLER MUST CHECK ITSELF: the poses (a NaN angle leaves no trace in any output); and, in the planar layout, the
+ *     disparities -- it can return a finite loss for a NaN or zero disparity (the gradients are then NaN: torch.isfinite on d_disp /
+ *     d_pose, or a GradScaler, sees it).  Nothing validates inputs on the device, because that would synchronise;
  *   - return value: 0 on success; SFM_ERR_* (<0) for a rejected argument; a positive value is
  *     a hipError_t from the launch.  sfm_last_error() returns a thread-local message.
  *     No exception or abort crosses the ABI.

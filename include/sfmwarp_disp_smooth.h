@@ -30,6 +30,10 @@ extern "C" {
  * |D(d/M)| = |Dd| / |M|: the value is the smoothness of d / M_b without a normalised copy.
  * edge = MEAN_ABS with normalize = 1 is Monodepth2's get_smooth_loss on disp / (mean + 1e-7); edge = ABS_MEAN with normalize = 0 is
  * compute_disp_smooth of models/base_model.py:144-155.
+ * Non-finite and degenerate inputs: a NaN disparity makes X_b, Y_b (and, with normalize, M_b) of that sample NaN, hence loss[s] and
+ * loss[n_scales]; with normalize every gradient of that sample is NaN, without it the gradient stays FINITE (it is sign(Dd) w c, and
+ * the sign of a NaN difference is taken as +-1): the loss, not the gradient, reports it.  A zero disparity among positive ones is
+ * an ordinary value.  Other samples' statistics and gradients keep their bits (tests/test_hostile_inputs_gpu.py).
  * M_b = 0 is not checked (a network's disparities are positive): the divisions then give +inf, or NaN where X_b = Y_b = 0, in
  * loss[s], loss[n_scales] and every gradient of that sample.
  * ---------------------------------------------------------------------------------------- */

@@ -5,6 +5,12 @@
  * include/sfmwarp_min_reproj.h and include/sfmwarp_disp_smooth.h for the same reason as those two: the tables that pin sfmwarp.h's
  * descriptors and pointer prototypes live in test files a feature does not edit.  FOLLOW-UP: fold this section into sfmwarp.h (and
  * _lib.FULL_RES_SYMBOLS into _lib.SYMBOLS) together with those tables.  SFM_ABI_VERSION is unchanged: nothing that existed moved.
+ *
+ * Non-finite and degenerate inputs (sfmwarp.h, "NON-FINITE AND DEGENERATE INPUTS"; tests/test_hostile_inputs_gpu.py): the taps of
+ * the in-kernel upsampling come from the pixel's coordinates, never from data.  A NaN, zero or infinite coarse disparity reaches
+ * the full-resolution pixels whose bilinear footprint reads it -- a tap of weight 0 included (0 x NaN) -- and no other pixel; there
+ * the operator path's rule holds (value 0 and valid 0 for a NaN position, NaN in d_disp of the footprint and in that sample's d_pose).
+ * The _up_ and _conv_ forms behave alike.
  */
 #ifndef SFMWARP_FULL_RES_H_
 #define SFMWARP_FULL_RES_H_

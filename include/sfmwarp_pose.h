@@ -7,6 +7,13 @@
  * tables that pin sfmwarp.h's prototypes live in test files a feature does not edit.  FOLLOW-UP: fold SfmPoseConv into the two
  * descriptors (and _lib.POSE_SYMBOLS into _lib.SYMBOLS) at the next change of SFM_ABI_VERSION.  SFM_ABI_VERSION is unchanged here:
  * nothing that existed moved.
+ *
+ * Non-finite and degenerate inputs (sfmwarp.h says what every entry point guarantees on them; tests/test_hostile_inputs_gpu.py):
+ * a NaN Euler angle is read as -pi (the clip is fminf(fmaxf(r, -pi), pi)) and receives the gradient 0; +-inf and 1e30 are +-pi, as
+ * in the reference.  An axis-angle vector with a NaN entry gives a NaN matrix; one of 1e30 a finite one (sinf / cosf of the norm).
+ * A NaN or infinite translation, or such an entry of a "matrix" pose, stays in T as it is; in the _conv_ warps every pixel of that
+ * (sample, source) then has a NaN position: value 0, valid 0, and NaN in d_disp, d_pose / d_T of that sample.  Other samples keep
+ * their bits.
  */
 #ifndef SFMWARP_POSE_H_
 #define SFMWARP_POSE_H_
