@@ -14,7 +14,7 @@
  *                           valid_mask = the sampling position lies inside the view in both coordinates.
  *   compute_pairwise_loss:  diff_depth = ((computed_depth - projected_depth).abs() / (computed_depth + projected_depth)).clamp(0, 1);
  *                           weight_mask = 1 - diff_depth (the self-discovered mask); the geometry loss is the mean of diff_depth
- *                           over valid_mask.  The mean and the weighting are left to the caller: two aten lines.
+ *                           over valid_mask.  The mean and the weighting are sfm_pairwise_* (include/sfmwarp_pairwise.h).
  *
  * Non-finite and degenerate inputs (sfmwarp.h, "NON-FINITE AND DEGENERATE INPUTS"; tests/test_hostile_inputs_gpu.py): positions are
  * those of sfm_warp_pyramid_*, so a pixel whose projected position is NaN has diff 0 and valid 0, nothing is scattered for it, and

@@ -183,6 +183,21 @@ class SfmDepthConsDesc(C.Structure):
     ]
 
 
+# include/sfmwarp_pairwise.h: the masked means of SC-SfMLearner's compute_pairwise_loss
+class SfmPairwiseDesc(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32), ("n_src", C.c_int32), ("n_scales", C.c_int32),
+        ("H", C.c_int32 * SFM_MAX_SCALES), ("W", C.c_int32 * SFM_MAX_SCALES),
+        ("detach_weight", C.c_int32), ("min_count_photo", C.c_int32), ("min_count_geom", C.c_int32),
+        ("weight", C.c_float * SFM_MAX_SCALES),
+        ("err", _FP * SFM_MAX_SCALES), ("diff", _FP * SFM_MAX_SCALES), ("valid", _FP * SFM_MAX_SCALES),
+        ("ident", _FP * SFM_MAX_SCALES), ("cmp", _FP * SFM_MAX_SCALES),
+        ("keep", C.c_void_p * SFM_MAX_SCALES),      # device int8_t*
+        ("loss", _FP), ("count", C.c_void_p), ("g_loss", _FP),      # count: device int32_t*
+        ("g_err", _FP * SFM_MAX_SCALES), ("g_diff", _FP * SFM_MAX_SCALES),
+    ]
+
+
 # SFMWARP_LIB selects another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SFMWARP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsfmwarp.so")
 
@@ -290,6 +305,14 @@ DEPTH_CONS_SYMBOLS = {
 }
 
 
+# every symbol declared in the side header include/sfmwarp_pairwise.h (to be folded into SYMBOLS together with that header)
+PAIRWISE_SYMBOLS = {
+    "sfm_pairwise_workspace_bytes": (_Z, [C.POINTER(SfmPairwiseDesc)]),
+    "sfm_pairwise_fwd": (_I, [C.POINTER(SfmPairwiseDesc), _V, _Z, _V]),
+    "sfm_pairwise_bwd": (_I, [C.POINTER(SfmPairwiseDesc), _V]),
+}
+
+
 class SfmWarpError(RuntimeError):
     """A launch failed inside libsfmwarp (positive return code = hipError_t)."""
 
@@ -301,7 +324,8 @@ def _load():
             "or `make -C sfm-learner-chainer_amd/csrc`. There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SMOOTH_SYMBOLS.items()) \
-            + list(FULL_RES_SYMBOLS.items()) + list(CONV_SYMBOLS.items()) + list(POSE_SYMBOLS.items()) + list(DEPTH_CONS_SYMBOLS.items()):
+            + list(FULL_RES_SYMBOLS.items()) + list(CONV_SYMBOLS.items()) + list(POSE_SYMBOLS.items()) + list(DEPTH_CONS_SYMBOLS.items()) \
+            + list(PAIRWISE_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

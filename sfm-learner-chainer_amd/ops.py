@@ -9,13 +9,13 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SfmDepthConsDesc, SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPhotoErrorDesc, SfmWarpFullResDesc, SfmWarpPyramidDesc, check, lib
+from ._lib import SfmDepthConsDesc, SfmDispSmoothDesc, SfmLossDesc, SfmMinReprojDesc, SfmPairwiseDesc, SfmPhotoErrorDesc, SfmWarpFullResDesc, SfmWarpPyramidDesc, check, lib
 
 __all__ = ["pose_proj_fwd", "pose_proj_bwd", "pose_proj_bwd_intrinsics", "warp_fwd", "warp_bwd", "warp_bwd_intrinsics", "sampler_fwd", "sampler_bwd",
            "interp_fwd", "interp_bwd", "resize", "resize_bwd", "pyramid", "disp_act_fwd", "disp_act_bwd", "FusedLoss", "warp_pyramid_fwd",
            "warp_pyramid_bwd", "photo_error_fwd", "photo_error_bwd", "min_reproj_fwd", "min_reproj_bwd",
            "disp_smooth_fwd", "disp_smooth_bwd", "warp_full_res_fwd", "warp_full_res_bwd", "pose_mat_fwd", "pose_mat_bwd",
-           "depth_consistency_fwd", "depth_consistency_bwd"]
+           "depth_consistency_fwd", "depth_consistency_bwd", "pairwise_fwd", "pairwise_bwd"]
 
 FLOAT32 = (torch.float32,)
 FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # what a network puts out, autocast included (torch_api casts them)
@@ -966,6 +966,122 @@ def min_reproj_bwd(winners, count, g_loss, n_err, weights, norm, shapes):
     d.count, d.g_loss = count.data_ptr(), g_loss.data_ptr()
     _launch(dev, lib.sfm_min_reproj_bwd, C.byref(d))
     return g_errs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the masked means of SC-SfMLearner's compute_pairwise_loss for every scale and source (include/sfmwarp_pairwise.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _pairwise_desc(errs, diffs, weights, min_counts, detach_weight):
+    """(descriptor with err, diff and every setting bound, the arrays it points at, B, n_src, [(h, w)], device) for pairwise_fwd / _bwd"""
+    if not isinstance(errs, (list, tuple)) or not isinstance(diffs, (list, tuple)):
+        raise TypeError("errs and diffs must be lists with one array per scale")
+    S = len(errs)
+    if len(diffs) != S or not 1 <= S <= _lib.SFM_MAX_SCALES:
+        raise TypeError("errs and diffs need one entry per scale (1..%d), got %d and %d" % (_lib.SFM_MAX_SCALES, S, len(diffs)))
+    if len(weights) != S:
+        raise TypeError("one weight per scale (1..%d), got %d weights for %d scales" % (_lib.SFM_MAX_SCALES, len(weights), S))
+    errs, diffs = _devs(errs, "errs", 4), _devs(diffs, "diffs", 4)
+    B, n_src = errs[0].shape[:2]
+    dev = errs[0].device
+    if not 1 <= n_src <= _lib.SFM_MAX_SRC:
+        raise TypeError("1..%d sources, got %d" % (_lib.SFM_MAX_SRC, n_src))
+    hw = [tuple(t.shape[2:]) for t in errs]
+    for s, (h, w) in enumerate(hw):
+        if tuple(errs[s].shape) != (B, n_src, h, w) or diffs[s].shape != errs[s].shape:
+            raise TypeError("scale %d: errs and diffs must be (B,n_src,h,w) = %s, got %s and %s"
+                            % (s, (B, n_src, h, w), tuple(errs[s].shape), tuple(diffs[s].shape)))
+    _one_device(dev, errs + diffs)
+    d = SfmPairwiseDesc()
+    d.B, d.n_src, d.detach_weight = B, n_src, int(bool(detach_weight))
+    d.min_count_photo, d.min_count_geom = (int(v) for v in min_counts)
+    _set_scales(d, hw)
+    for s, w in enumerate(weights):
+        d.weight[s] = float(w)
+    for field, arrays in ((d.err, errs), (d.diff, diffs)):
+        _point(field, arrays)
+    return d, (errs, diffs), B, n_src, hw, dev
+
+
+def _pairwise_maps(ts, name, errs):
+    """None, or one float32 array of the shape of errs[s] per scale"""
+    if ts is None:
+        return []
+    if not isinstance(ts, (list, tuple)) or len(ts) != len(errs):
+        raise TypeError("%s needs one entry per scale" % name)
+    ts = _devs(ts, name, 4)
+    for s, t in enumerate(ts):
+        if t.shape != errs[s].shape:
+            raise TypeError("%s[%d] must be (B,n_src,h,w) = %s, got %s" % (name, s, tuple(errs[s].shape), tuple(t.shape)))
+    return ts
+
+
+def pairwise_fwd(errs, diffs, valids, idents, cmps, weights, min_counts, detach_weight):
+    """Per (scale, source) the mean of err * (1 - diff) and of diff over the kept pixels of the whole batch, and their weighted totals,
+    in two launches (sfm_pairwise_fwd): errs[s], diffs[s] (B,n_src,h,w) -- what `photo_error_fwd` returns for the warped pyramid and
+    `depth_consistency_fwd` for the same pose --; valids None or a list with (B,n_src,h,w) or None per scale (a pixel with
+    valid <= 0 is dropped); idents None (no auto-mask) or [(B,n_src,h,w)], the errors of the unwarped sources: a pixel is kept only
+    where cmps[s] (None: errs[s]) is strictly below it.  weights: one per scale; min_counts = (photo, geometry): a mean over at most
+    that many pixels is 0; detach_weight: looked at by the backward only.
+    -> (loss (2*S*n_src+2,) float32: photo[s*n_src+i], geom[s*n_src+i], photo_total, geom_total; count (S*n_src,) int32: the kept
+    pixels; [keep_s (B,n_src,h,w) int8]).  Sums are fp64 in a fixed order, no atomics: the same bits on every call.  A rejection by
+    the library (a negative weight or min_count) is a ValueError with sfm_last_error() as its message."""
+    d, held, B, n_src, hw, dev = _pairwise_desc(errs, diffs, weights, min_counts, detach_weight)
+    errs, S = held[0], len(hw)
+    valids = [None] * S if valids is None else list(valids)
+    if len(valids) != S:
+        raise TypeError("valids needs one entry per scale")
+    valids = [None if t is None else _dev(t, "valids[%d]" % s, 4) for s, t in enumerate(valids)]
+    for s, t in enumerate(valids):
+        if t is not None and t.shape != errs[s].shape:
+            raise TypeError("valids[%d] must be (B,n_src,h,w) = %s, got %s" % (s, tuple(errs[s].shape), tuple(t.shape)))
+    idents, cmps = _pairwise_maps(idents, "idents", errs), _pairwise_maps(cmps, "cmps", errs)
+    if cmps and not idents:
+        raise TypeError("cmps without idents: there is nothing to compare them with")
+    _one_device(dev, [t for t in valids if t is not None] + idents + cmps)
+    loss = torch.empty((2 * S * n_src + 2,), dtype=torch.float32, device=dev)
+    count = torch.empty((S * n_src,), dtype=torch.int32, device=dev)
+    keeps = [torch.empty((B, n_src, h, w), dtype=torch.int8, device=dev) for h, w in hw]
+    for field, arrays in ((d.valid, valids), (d.ident, idents), (d.cmp, cmps), (d.keep, keeps)):
+        _point(field, arrays)
+    d.loss, d.count = loss.data_ptr(), count.data_ptr()
+    if B == 0:      # the mean of nothing, as the library defines it for a pair with nothing kept; nothing to launch
+        return loss.zero_(), count.zero_(), keeps
+    nbytes = lib.sfm_pairwise_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        check(lib.sfm_pairwise_fwd(C.byref(d), None, 0, None))   # re-run the validation for its message
+        raise ValueError(_lib.last_error() or "invalid pairwise descriptor")
+    ws, ptr, have = _place_workspace(None, nbytes, dev)
+    _launch(dev, lib.sfm_pairwise_fwd, C.byref(d), C.c_void_p(ptr), have)
+    return loss, count, keeps
+
+
+def pairwise_bwd(errs, diffs, keeps, count, g_loss, weights, min_counts, detach_weight, want_g_diff=True):
+    """The backward of `pairwise_fwd` for the upstream gradients g_loss (2*S*n_src+2,) of its `loss`, ONE launch (sfm_pairwise_bwd):
+    keeps and count as the forward returned them -> ([g_err_s (B,n_src,h,w)], [g_diff_s (B,n_src,h,w)] or None without
+    `want_g_diff`): g_err = (1 - diff) * cp and g_diff = cg - err * cp (cg alone with `detach_weight`) at a kept pixel, 0 elsewhere,
+    cp / cg = (g_loss[photo / geom s,i] + weights[s] * g_loss[photo / geom total]) / max(count, 1), 0 where count <= min_count.
+    The kernel reads count and g_loss on the device: nothing syncs."""
+    d, held, B, n_src, hw, dev = _pairwise_desc(errs, diffs, weights, min_counts, detach_weight)
+    S = len(hw)
+    if not isinstance(keeps, (list, tuple)) or len(keeps) != S:
+        raise TypeError("keeps needs one entry per scale")
+    for s, (t, (h, w)) in enumerate(zip(keeps, hw)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int8 or tuple(t.shape) != (B, n_src, h, w) or not t.is_contiguous():
+            raise TypeError("keeps[%d] must be a contiguous int8 array (B,n_src,h,w) = %s" % (s, (B, n_src, h, w)))
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or tuple(count.shape) != (S * n_src,) or not count.is_contiguous():
+        raise TypeError("count must be a contiguous int32 array (%d,)" % (S * n_src))
+    g_loss = _dev(g_loss, "g_loss", 1)
+    if tuple(g_loss.shape) != (2 * S * n_src + 2,):
+        raise TypeError("g_loss must be (%d,), got %s" % (2 * S * n_src + 2, tuple(g_loss.shape)))
+    _one_device(dev, list(keeps) + [count, g_loss])
+    shapes = [(B, n_src, h, w) for h, w in hw]
+    g_errs = _empty(shapes, dev)
+    g_diffs = _empty(shapes, dev) if want_g_diff else None
+    for field, arrays in ((d.keep, keeps), (d.g_err, g_errs), (d.g_diff, g_diffs or ())):
+        _point(field, arrays)
+    d.count, d.g_loss = count.data_ptr(), g_loss.data_ptr()
+    _launch(dev, lib.sfm_pairwise_bwd, C.byref(d))
+    return g_errs, g_diffs
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

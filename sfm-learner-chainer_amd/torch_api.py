@@ -16,6 +16,10 @@ grad_fn.  This module hands those outputs to libsfmwarp and the gradients it com
   min_reprojection                    the stage behind it: per pixel the minimum over the sources, the auto-mask against the unwarped
                                       sources and the mean of every scale (ops.min_reproj_fwd / ops.min_reproj_bwd)
   min_reprojection_loss               warp_pyramid -> photometric_error -> min_reprojection as one call and ONE autograd node
+  depth_consistency                   SC-SfMLearner's diff_depth of every (scale, source) (ops.depth_consistency_fwd / _bwd)
+  pairwise_mean                       the stage behind it and photometric_error: the masked means of compute_pairwise_loss per (scale,
+                                      source), with the auto-mask and the mean_on_mask threshold (ops.pairwise_fwd / ops.pairwise_bwd)
+  sc_sfm_loss                         SC-SfMLearner's objective, both directions: one autograd node per direction
   multi_scale_intrinsics              datasets/kitti/kitti_raw_transformed.py:76-93, differentiable (plain torch)
   disp_activation                     models/disp_net.py:104-122 (ops.disp_act_fwd / ops.disp_act_bwd)
   resize_images / resize_like         F.resize_images as DispNet's decoder differentiates it, models/disp_net.py:11-14,105,111,117
@@ -48,7 +52,7 @@ from ._lib import SfmLossDesc, lib
 __all__ = ["sfm_learner_loss", "SFMLearnerLoss", "projective_inverse_warp", "disp_activation", "resize_images", "resize_like",
            "scale_arrays_into", "multi_scale_intrinsics", "warp_pyramid", "photometric_error",
            "min_reprojection", "min_reprojection_loss", "disparity_smoothness", "warp_full_res", "pose_matrix",
-           "depth_consistency"]
+           "depth_consistency", "pairwise_mean", "sc_sfm_loss"]
 
 _ALIGN = 64                  # floats: every array inside a per-call buffer starts on a 256-byte boundary
 _MAX_ARRAYS = 32             # sfm_scale_arrays
@@ -718,7 +722,8 @@ def depth_consistency(pred_disps, src_disps, intrinsics, pred_poses, *, return_v
     masks (1.0 where the sample passes both strict in-view tests, else 0.0), with `return_depths` also the S computed and the S
     projected depths: (diff, valid, computed, projected) without the lists not asked for; only diff is differentiable.
 
-    It adds no reduction.  SC-SfMLearner's geometry loss and its self-discovered mask are two aten lines on the result:
+    It adds no reduction.  SC-SfMLearner's geometry loss and its self-discovered mask are `pairwise_mean` on the result (and the
+    whole objective `sc_sfm_loss`), or two aten lines:
       geometry = sum((d * v).sum() / v.sum().clamp(min=1) for d, v in zip(diff, valid))
       weighted = [err_s * (1 - d) for err_s, d in zip(photometric_error_maps, diff)]
 
@@ -1242,6 +1247,292 @@ def min_reprojection_loss(tgt_img, src_imgs, intrinsics, pred_disps, pred_poses,
     cfg = (float(ssim_rate), bool(auto_mask), weights, norm, smooth, ssim_padding, upsample, pc)
     _lib.min_reproj_norm_id(norm)
     return node.apply(tgt.detach(), src.detach().view(B, 3 * n_src, H, W), K, cfg, S, *disps, *poses)
+
+
+def _unit_weights(weights, S):
+    """`weights` of pairwise_mean / sc_sfm_loss as a tuple of S floats; None: 1.0 each -- SC-SfMLearner adds the scales unweighted
+    (NOT the 2**-s of `min_reprojection`)"""
+    if weights is None:
+        return (1.0,) * S
+    weights = tuple(float(w) for w in weights)
+    if len(weights) != S:
+        raise TypeError("weights: one per scale, got %d for %d scales" % (len(weights), S))
+    return weights
+
+
+def _min_counts(min_count):
+    try:
+        photo, geom = (int(v) for v in min_count)
+    except (TypeError, ValueError):
+        raise ValueError("min_count must be (photo, geometry), two integers >= 0, got %r" % (min_count,)) from None
+    if photo < 0 or geom < 0:
+        raise ValueError("min_count must be (photo, geometry), two integers >= 0, got %r" % (min_count,))
+    return photo, geom
+
+
+def _pairwise_g_loss(n_pairs, g_pt, g_gt, g_p, g_g, device):
+    """(2*n_pairs+2,) float32: the upstream gradients in the layout sfm_pairwise_bwd reads; None is zero.  On the device."""
+    parts = []
+    for g, n in ((g_p, n_pairs), (g_g, n_pairs), (g_pt, 1), (g_gt, 1)):
+        parts.append(torch.zeros((n,), dtype=torch.float32, device=device) if g is None else g.to(torch.float32).reshape(n))
+    return torch.cat(parts)
+
+
+class _PairwiseMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, weights, min_count, detach_weight, bound, has_ident, has_cmp, *arrays):
+        errs, diffs, rest = list(arrays[:S]), list(arrays[S:2 * S]), list(arrays[2 * S:])
+        valids = [rest.pop(0) if on else None for on in bound]
+        idents = rest[:S] if has_ident else None
+        cmps = rest[S:2 * S] if has_cmp else None
+        loss, count, keeps = ops.pairwise_fwd(errs, diffs, valids, idents, cmps, weights, min_count, detach_weight)
+        n = errs[0].shape[1]
+        ctx.save_for_backward(count, *errs, *diffs, *keeps)
+        ctx.cfg = (S, n, weights, min_count, detach_weight, len(arrays))
+        ctx.mark_non_differentiable(*keeps)
+        ctx.set_materialize_grads(False)
+        N = S * n
+        return (loss[2 * N], loss[2 * N + 1], loss[:N].view(S, n), loss[N:2 * N].view(S, n)) + tuple(keeps)
+
+    @staticmethod
+    def backward(ctx, g_pt, g_gt, g_p, g_g, *_):
+        S, n, weights, min_count, detach_weight, n_arrays = ctx.cfg
+        if g_pt is None and g_gt is None and g_p is None and g_g is None:
+            return (None,) * (7 + n_arrays)
+        count, rest = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+        errs, diffs, keeps = rest[:S], rest[S:2 * S], rest[2 * S:]
+        want = any(ctx.needs_input_grad[7 + S:7 + 2 * S])
+        g_loss = _pairwise_g_loss(S * n, g_pt, g_gt, g_p, g_g, count.device)
+        g_errs, g_diffs = ops.pairwise_bwd(errs, diffs, keeps, count, g_loss, weights, min_count, detach_weight, want_g_diff=want)
+        return (None,) * 7 + tuple(g_errs) + (tuple(g_diffs) if want else (None,) * S) + (None,) * (n_arrays - 2 * S)
+
+
+def pairwise_mean(errs, diffs, *, valid=None, ident=None, cmp=None, weights=None, min_count=(0, 0), detach_weight=False):
+    """The last stage of SC-SfMLearner's compute_pairwise_loss on the library's maps: per (scale, source), over the whole batch, the
+    mean of err * (1 - diff) -- the photometric error under the self-discovered mask -- and of diff -- the geometry-consistency loss
+    -- over the kept pixels, every scale and source in two launches (ops.pairwise_fwd) and one backward (ops.pairwise_bwd); what
+    INTEGRATION.md spells as (e * (1 - d) * v).sum() / v.sum().clamp(min=1) and (d * v).sum() / v.sum().clamp(min=1) per scale.
+
+    errs, diffs: lists of S tensors (B,n,h_s,w_s) -- what `photometric_error` returns for the list `warp_pyramid` returns, and what
+      `depth_consistency` returns; float32, bfloat16 or float16 on a ROCm device (computed in float32, each gradient returned in its
+      input's dtype);
+    valid: None, or a list of S entries, each (B,n,h_s,w_s) float32 or None -- `warp_pyramid(..., return_valid=True)`: a pixel with
+      valid <= 0 is dropped;
+    ident: None (no auto-mask) or a list of S tensors (B,n,h_s,w_s) float32, the error of UNWARPED source i against the target: a
+      pixel is kept only where `cmp` -- None: errs itself -- is strictly below it (a tie or a NaN drops the pixel).  SC-SfMLearner
+      compares the channel-mean L1 of the warped and of the unwarped source: photometric_error at ssim_rate=0 as `cmp` and `ident`;
+    weights: one per scale; None means 1.0 for every scale, as SC-SfMLearner adds them -- NOT the 2**-s of `min_reprojection`;
+    min_count=(photo, geometry): a mean over at most that many pixels is 0, with a zero gradient -- mean_on_mask's
+      `mask.sum() > 10000` on a mask expanded to the channels is (3333, 10000) on this library's channel-mean error map; (0, 0) is
+      the clamp(min=1) of INTEGRATION.md;
+    detach_weight: the weight 1 - diff carries no gradient to `diffs` (the geometry mean still does).
+
+    Returns (photo_total, geom_total, photo, geom, keeps): the totals, 0-d, = sum_s weights[s] * sum_i photo[s, i] (and geom); photo
+    and geom (S,n), the mean of each (scale, source); all four differentiable with respect to `errs` and `diffs` ONLY; keeps, a list of
+    S int8 maps (B,n,h_s,w_s), 1 where the pixel is kept.  Dropped pixels are excluded by selection: a NaN there changes nothing.
+    Sums run in fp64 in a fixed order: the same bits on every call.  Nothing reads a device value on the host: it runs under
+    torch.cuda.graph capture."""
+    if not isinstance(errs, (list, tuple)) or not isinstance(diffs, (list, tuple)):
+        raise TypeError("errs and diffs must be lists of (B,n,h,w) tensors, one per scale")
+    S = len(errs)
+    if not 1 <= S <= _lib.SFM_MAX_SCALES or len(diffs) != S:
+        raise TypeError("1..%d scales, and as many diffs as errs: got %d and %d" % (_lib.SFM_MAX_SCALES, S, len(diffs)))
+    min_count = _min_counts(min_count)
+    weights = _unit_weights(weights, S)
+    xs = [_dev_float(t, "errs[%d]" % s, 4) for s, t in enumerate(errs)]
+    ds = [_dev_float(t, "diffs[%d]" % s, 4) for s, t in enumerate(diffs)]
+    valid = [None] * S if valid is None else list(valid)
+    if len(valid) != S or (ident is not None and len(ident) != S) or (cmp is not None and len(cmp) != S):
+        raise TypeError("valid, ident and cmp need one entry per scale (%d)" % S)
+    if cmp is not None and ident is None:
+        raise TypeError("cmp without ident: there is nothing to compare it with")
+    bound = tuple(v is not None for v in valid)
+    vs = [ops._dev(v, "valid[%d]" % s, 4).detach() for s, v in enumerate(valid) if v is not None]
+    ids = [] if ident is None else [t.detach() for t in ops._devs(ident, "ident", 4)]
+    cs = [] if cmp is None else [t.detach() for t in ops._devs(cmp, "cmp", 4)]
+    out = _PairwiseMean.apply(S, weights, min_count, bool(detach_weight), bound, ident is not None, cmp is not None, *xs, *ds, *vs, *ids, *cs)
+    return out[0], out[1], out[2], out[3], list(out[4:])
+
+
+_AUTO_MASKS = {False: None, None: None, "error": "error", "l1": "l1"}
+
+
+class _ScSfmLoss(torch.autograd.Function):
+    """warp_pyramid -> photometric_error -> depth_consistency -> pairwise_mean (-> disparity_smoothness) as ONE node: one direction
+    of compute_photo_and_geometry_loss for every scale and source."""
+
+    @staticmethod
+    def forward(ctx, tgt, src, K, cfg, S, *arrays):
+        ssim_rate, auto_mask, with_mask, detach_weight, min_count, weights, geometry_weight, smooth, pad, pc = cfg
+        disps, src_disps, poses = list(arrays[:S]), list(arrays[S:2 * S]), list(arrays[2 * S:])
+        B, n_src = src.shape[0], len(poses)
+        pyr = ops.pyramid_hwc(src, S)
+        warped, valid = ops.warp_pyramid_fwd(pyr, disps, poses, K, "hwc", True, **_pose_kw(pc))
+        tgts = ops.pyramid(tgt, S)
+        errs = ops.photo_error_fwd(warped, tgts, ssim_rate, pad)
+        idents = cmps = None
+        if auto_mask is not None:     # the identity error: the planar source pyramid is (B,n_src,3,h,w) byte for byte
+            plain = [p.view(B, n_src, 3, p.shape[2], p.shape[3]) for p in ops.pyramid(src, S)]
+            if auto_mask == "l1":     # SC-SfMLearner's own test: the channel-mean L1 of the warped against that of the unwarped source
+                cmps = ops.photo_error_fwd(warped, tgts, 0.0, pad)
+                idents = ops.photo_error_fwd(plain, tgts, 0.0, pad)
+            else:
+                idents = ops.photo_error_fwd(plain, tgts, ssim_rate, pad)
+        diffs = ops.depth_consistency_fwd(disps, src_disps, poses, K, **_pose_kw(pc))
+        loss, count, keeps = ops.pairwise_fwd(errs, diffs, valid, idents, cmps, weights, min_count, detach_weight)
+        N = S * n_src
+        photo, geom = loss[2 * N], loss[2 * N + 1]
+        saved = [K, count, *pyr, *disps, *src_disps, *poses, *warped, *tgts, *errs, *diffs, *keeps]
+        if not with_mask:             # the photometric means of the SAME stage on a zero diff: e * (1.0f - 0.0f) is e, bit for bit
+            zeros = [torch.zeros_like(d) for d in diffs]
+            loss0, count, keeps = ops.pairwise_fwd(errs, zeros, valid, idents, cmps, weights, min_count, True)
+            photo = loss0[2 * N]
+            saved += zeros
+        total = photo + geometry_weight * geom
+        if smooth is not None:        # on the target pyramid this node holds anyway: the RAW disparities
+            sm_loss, stats = ops.disp_smooth_fwd(disps, tgts, *smooth)
+            saved.append(stats)
+            total = total + sm_loss[S]
+        ctx.save_for_backward(*saved)
+        ctx.cfg, ctx.S, ctx.n_src = cfg, S, n_src
+        ctx.set_materialize_grads(False)
+        return total, photo, geom
+
+    @staticmethod
+    def backward(ctx, g_total, g_photo, g_geom):
+        ssim_rate, auto_mask, with_mask, detach_weight, min_count, weights, geometry_weight, smooth, pad, pc = ctx.cfg
+        S, n_src = ctx.S, ctx.n_src
+        if g_total is None and g_photo is None and g_geom is None:
+            return (None,) * (5 + 2 * S + n_src)
+        K, count, rest = ctx.saved_tensors[0], ctx.saved_tensors[1], list(ctx.saved_tensors[2:])
+        take = lambda k: [rest.pop(0) for _ in range(k)]
+        pyr, disps, src_disps, poses = take(S), take(S), take(S), take(n_src)
+        warped, tgts, errs, diffs, keeps = take(S), take(S), take(S), take(S), take(S)
+        zeros = take(S) if not with_mask else None
+        dev, N = count.device, S * n_src
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        gt = None if g_total is None else g_total.to(torch.float32)
+        g_pt = zero if gt is None else gt
+        g_gt = zero if gt is None else geometry_weight * gt
+        if g_photo is not None:
+            g_pt = g_pt + g_photo.to(torch.float32)
+        if g_geom is not None:
+            g_gt = g_gt + g_geom.to(torch.float32)
+        if with_mask:
+            g_errs, g_diffs = ops.pairwise_bwd(errs, diffs, keeps, count, _pairwise_g_loss(N, g_pt, g_gt, None, None, dev), weights,
+                                               min_count, detach_weight)
+        else:                         # the two calls of the forward: the photometric one on the zero diff, the geometry one without the weight
+            g_errs, _ = ops.pairwise_bwd(errs, zeros, keeps, count, _pairwise_g_loss(N, g_pt, None, None, None, dev), weights, min_count,
+                                         True, want_g_diff=False)
+            _, g_diffs = ops.pairwise_bwd(errs, diffs, keeps, count, _pairwise_g_loss(N, None, g_gt, None, None, dev), weights, min_count,
+                                          True)
+        d_warped = ops.photo_error_bwd(warped, tgts, ssim_rate, g_errs, pad)
+        d_disps, d_poses = ops.warp_pyramid_bwd(pyr, disps, poses, K, "hwc", d_warped, **_pose_kw(pc))
+        want = any(ctx.needs_input_grad[5 + S:5 + 2 * S])      # src_disps that do not require grad: the kernel without the scatter
+        c_disps, c_poses, d_src = ops.depth_consistency_bwd(disps, src_disps, poses, K, g_diffs, want_d_src_disp=want, **_pose_kw(pc))
+        for a, b in zip(d_disps + d_poses, c_disps + c_poses):      # float32, the warp's first: warp + depth_consistency
+            a.add_(b)
+        if smooth is not None:        # the smoothness gradient is added in place by its kernel: no aten call
+            ops.disp_smooth_bwd(disps, tgts, rest[0], _g_loss(S, gt, None, dev), *smooth, out=d_disps)
+        return (None,) * 5 + tuple(d_disps) + (tuple(d_src) if want else (None,) * S) + tuple(d_poses)
+
+
+def sc_sfm_loss(tgt_img, src_imgs, intrinsics, tgt_disps, src_disps, pred_poses, *, ssim_rate=0.85, geometry_weight=0.5, smooth_weight=0.0,
+                auto_mask=False, with_mask=True, detach_weight=False, min_count=(0, 0), weights=None, bidirectional=True,
+                ssim_padding="zero", pose_format="euler", invert=None, depth_range=None, smooth_normalize=True, smooth_edge="mean_abs"):
+    """SC-SfMLearner's objective (Bian et al., NeurIPS 2019: compute_photo_and_geometry_loss) on this library's warp in one call, ONE
+    autograd node per direction:
+
+      total = photo + geometry_weight * geometry (+ smooth),    added in float32 in that order
+
+    with photo the sum over the scales (times weights[s]) and the sources of the mean of err * (1 - diff_depth) over the kept pixels,
+    geometry that of diff_depth, err = ssim_rate * SSIM + (1 - ssim_rate) * L1 of `photometric_error`, diff_depth of
+    `depth_consistency` and the means of `pairwise_mean`; a pixel is kept where the warp is in view and it passes the auto-mask.
+
+    tgt_img (B,3,H,W), src_imgs (B,n_src,3,H,W) float32: constants; intrinsics (B,S,3,3): a constant (TypeError if it requires grad);
+    tgt_disps: S tensors (B,1,H>>s,W>>s), the network on the target frame; src_disps: S tensors (B,n_src,H>>s,W>>s), the SAME network
+    on each source frame; pred_poses: n_src tensors (B,6) or one packed (B,6*n_src) tensor.  Predictions are float32, bfloat16 or
+    float16, each gradient returned in its input's dtype.
+
+    auto_mask: False; "l1" -- SC-SfMLearner's own test: the pixel is kept where the channel-mean L1 of the warped source is strictly
+      below that of the unwarped one (the two error maps at ssim_rate = 0, `cmp` / `ident` of `pairwise_mean`); or "error" -- the
+      unwarped error at `ssim_rate` compared against err itself (Monodepth2's form of the test);
+    with_mask=False: the photometric term is the plain masked mean of err.  The stage runs twice, once more on a zero diff -- e *
+      (1.0f - 0.0f) is e, bit for bit -- and the backward runs its launch twice; the geometry term is unchanged;
+    detach_weight, min_count, weights: those of `pairwise_mean`; weights=None adds the scales unweighted;
+    smooth_weight > 0 adds smooth_weight * the total of `disparity_smoothness` (per-scale weights float32(smooth_weight * weights[s]),
+      `smooth_normalize`, `smooth_edge`) of the TARGET frame on the target pyramid, in the first direction's node;
+    ssim_padding, pose_format, invert, depth_range: those of `min_reprojection_loss`; depth_range acts on every disparity.
+
+    One direction, forward: the source pyramid, `warp_pyramid`'s launch with its valid masks, the target pyramid, `photometric_error`'s
+    launch (with auto_mask two more, "l1", or one more, "error"), `depth_consistency`'s, `pairwise_mean`'s two, optionally the
+    smoothness' two.  Backward: one launch of pairwise_mean, one of photometric_error, the warp's two, depth_consistency's two -- its
+    scatter into d_src_disp only where src_disps require grad -- then d_disp and d_pose of the warp and of depth_consistency added in
+    float32, the warp's first, and the smoothness gradient added in place by its own launch.  The values are those of the stages called
+    one after the other, bit for bit; nothing reads a device value on the host, so the step can be captured in a graph.
+
+    bidirectional=True (the default) adds the second direction of compute_photo_and_geometry_loss as a second node: every source
+    becomes the target of a batch of B*n_src samples with ONE reference frame, the original target -- its own src_disps are the target
+    disparities, tgt_disps the reference's, the pose of its pair is used with the inversion flag flipped, the intrinsics are repeated.
+    The reshapes are plain aten; the three scalars of the two directions are added in float32, the first direction's first.  The
+    second direction's means run over the B*n_src pairs TOGETHER (one mean per scale, not one per source), which is the
+    count-weighted average of the per-source means the loop of INTEGRATION.md adds up.  It needs one inversion flag for all sources
+    (invert=None or all equal: ValueError otherwise) and a 6-vector pose: pose_format="matrix" with bidirectional=True is a
+    ValueError -- invert the matrices and call each direction yourself.
+
+    Returns (total, photo, geometry), three 0-d tensors.
+
+    Out of scope: SC-SfMLearner's clamp(0, 1) of the per-channel L1 in front of the channel mean.  `photometric_error` does not have
+    it, and it never acts on images in [0, 1]."""
+    _lib.ssim_padding_id(ssim_padding, "ssim_padding")
+    if isinstance(auto_mask, torch.Tensor) or auto_mask not in _AUTO_MASKS:
+        raise ValueError("auto_mask must be False, 'error' or 'l1', got %r" % (auto_mask,))
+    auto_mask = _AUTO_MASKS[auto_mask]
+    pc = _pose_conv_args(src_imgs, pose_format, invert, depth_range)
+    if bidirectional and pose_format == "matrix":
+        raise ValueError("pose_format='matrix' with bidirectional=True: invert the matrices and call each direction yourself")
+    if bidirectional and pc[1] is not None and len(set(pc[1])) > 1:
+        raise ValueError("bidirectional=True needs one inversion flag for all sources, got invert=%r" % (invert,))
+    min_count = _min_counts(min_count)
+    geometry_weight = float(geometry_weight)
+    if smooth_weight:
+        smooth_weight = float(smooth_weight)
+        if not smooth_weight >= 0.0:
+            raise ValueError("smooth_weight must be >= 0, got %r" % (smooth_weight,))
+        _lib.disp_smooth_edge_id(smooth_edge)
+    tgt = ops._dev(tgt_img, "tgt_img", 4)
+    if isinstance(tgt_disps, torch.Tensor) or isinstance(src_disps, torch.Tensor):
+        raise TypeError("tgt_disps and src_disps are lists with one tensor per scale")
+    src, K, disps, poses, _ = _step_inputs(src_imgs, intrinsics, tgt_disps, pred_poses, tgt, pose_format=pose_format)
+    if K.requires_grad:
+        raise TypeError("sc_sfm_loss does not differentiate the intrinsics: detach them")
+    B, n_src, _, H, W = src.shape
+    S = len(disps)
+    if len(src_disps) != S:
+        raise TypeError("as many src_disps as tgt_disps: got %d and %d" % (len(src_disps), S))
+    srcs = []
+    for s, t in enumerate(src_disps):
+        t = _dev_float(t, "src_disps[%d]" % s, 4)
+        if tuple(t.shape) != (B, n_src, H >> s, W >> s) or t.device != tgt.device:
+            raise TypeError("src_disps[%d] must be (B,n_src,H>>%d,W>>%d) = %s on %s, got %s"
+                            % (s, s, s, (B, n_src, H >> s, W >> s), tgt.device, tuple(t.shape)))
+        srcs.append(t)
+    weights = _unit_weights(weights, S)
+    smooth = (tuple(smooth_weight * w for w in weights), bool(smooth_normalize), smooth_edge) if smooth_weight else None
+    head = (float(ssim_rate), auto_mask, bool(with_mask), bool(detach_weight), min_count, weights, geometry_weight)
+    tgt, src = tgt.detach(), src.detach()
+    out = _ScSfmLoss.apply(tgt, src.view(B, 3 * n_src, H, W), K, head + (smooth, ssim_padding, pc), S, *disps, *srcs, *poses)
+    if not bidirectional:
+        return out
+    # the second direction: sample b * n_src + i is source i of sample b as the target, the original target as its one reference
+    M = B * n_src
+    flipped = (not (pc[1][0] if pc[1] is not None else False),)
+    back = _ScSfmLoss.apply(src.reshape(M, 3, H, W), tgt[:, None].expand(B, n_src, 3, H, W).reshape(M, 3, H, W),
+                            K.repeat_interleave(n_src, dim=0), head + (None, ssim_padding, (pc[0], flipped, pc[2])), S,
+                            *[t.reshape(M, 1, t.shape[2], t.shape[3]) for t in srcs],
+                            *[t.expand(B, n_src, t.shape[2], t.shape[3]).reshape(M, 1, t.shape[2], t.shape[3]) for t in disps],
+                            torch.stack(poses, 1).reshape(M, 6))
+    return tuple(a + b for a, b in zip(out, back))
 
 
 def multi_scale_intrinsics(K, n_scales):
